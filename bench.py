@@ -27,6 +27,20 @@ the PCIe-inclusive pipeline rate (pinned host buffers -> H2D -> kernels ->
 D2H, pixpath.pipeline, never `value`), and the CPU baseline (the oracle's C
 restatement, scale and SI/TI timed separately on host threads).
 
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up,
+times the N steps and prints the result line with the fields the timed steps
+themselves give (value, ms_per_step, the HIP-event kernel times).  Everything
+that takes runs of its own -- the PCIe pipeline, the SI/TI file hook, the
+end-to-end AVPVS line, the CPU baseline, and in the other workloads the canvas
+chain, the FFV1 decode / concurrent / writer-lane lines and the reference-shape
+stream decode -- runs only with --full (the --no-* options then drop single
+parts of it, as before).
+
+--dump-outputs DIR writes, after the timed steps, what the timed path computed
+in its last step as DIR/<name>.npy (float32 / float64, every value finite; a
+fixed seeded sample of the frames: well under 64 MB).  The inputs are seeded,
+so two runs with the same arguments dump the same arrays.
+
 Other workloads (profiles only, same schema): --workload config3-10 /
 config3-8 (2160p -> 1080p yuv422p10le bicubic) and config4 (stall frames).
 """
@@ -105,6 +119,12 @@ def parse():
     ap.add_argument("--workload", default="config2", choices=sorted(list(WORKLOADS) + ["config4", "ffv1"]))
     ap.add_argument("--ffv1-slices", default="8x8", help="FFV1 slice grid (workload ffv1)")
     ap.add_argument("--ffv1-concurrent", type=int, default=4, help="PVS batches in flight for the concurrent FFV1 line")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: PCIe pipeline, SI/TI file hook, "
+                         "end-to-end AVPVS, CPU baseline (config2/3); canvas chain (config4); decode, concurrent, "
+                         "writer lanes, CPU baseline, reference-shape streams (ffv1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (a fixed sample) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pipeline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=6.0, help="per CPU-baseline stage at full width")
@@ -606,6 +626,54 @@ def e2e_avpvs(wl, n_frames, dev, n_pvs=4, depth=None, shared=True):
                     "(runs_s), single_pvs: the best of 3" % (n_pvs, n_frames, depth, n_pvs)}
 
 
+DUMP_SEED = 910
+DUMP_FRAMES = 16   # frames sampled per dumped batch
+DUMP_ROWS = 64     # rows sampled per plane of a sampled frame
+
+
+def sample_frames(fb, seed=DUMP_SEED):
+    """A fixed, seeded sample of a FrameBatch for --dump-outputs: DUMP_FRAMES
+    frames (the first and the last among them), and of every plane of those
+    DUMP_ROWS whole rows (the first and the last among them).  Returns
+    {"plane<p>": float32 [frames, rows, cols], "frames": ..., "rows<p>": ...}:
+    a 1080p yuv422p10le batch gives 15.7 MB."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+
+    def pick(n, k):
+        if n <= k:
+            return np.arange(n)
+        mid = rng.choice(np.arange(1, n - 1), size=k - 2, replace=False)
+        return np.sort(np.concatenate([[0, n - 1], mid]))
+    frames = pick(fb.n, DUMP_FRAMES)
+    out = {"frames": frames.astype(np.float64)}
+    for p in range(len(fb.planes)):
+        v = fb.view(p)
+        rows = pick(v.shape[1], DUMP_ROWS)
+        out["rows%d" % p] = rows.astype(np.float64)
+        out["plane%d" % p] = np.stack([v[int(f)].cpu().numpy()[rows] for f in frames]).astype(np.float32)
+    return out
+
+
+def dump_outputs(path, arrays):
+    """arrays: {name: numpy array} -> path/<name>.npy, float32 or float64."""
+    import numpy as np
+    out = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        if not np.isfinite(a).all():
+            raise ValueError("--dump-outputs: %s holds a value that is not finite" % name)
+        out[name] = a
+    total = sum(a.nbytes for a in out.values())
+    if total > 64 << 20:
+        raise ValueError("--dump-outputs: %d bytes exceed 64 MB" % total)
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def make_inputs(wl, n, seed, dev):
     import torch
     from pixpath.frames import FrameBatch
@@ -723,6 +791,21 @@ def main():
     per_rank = batch.gather_values(len(mine), rank, world)
     if rank != 0:
         return 0
+    if args.dump_outputs:
+        # the last step's outputs as its caller holds them: the AVPVS batches
+        # still in the output buffers (the last PVSes of this rank) and the
+        # gathered per-frame SI/TI of every PVS
+        arrays = {}
+        last = {(i % len(outs)): pid for i, pid in enumerate(mine)}
+        for slot, pid in sorted(last.items()):
+            for k, a in sample_frames(outs[slot], DUMP_SEED + slot).items():
+                arrays["avpvs_%s_%s" % (pid, k)] = a
+        if gathered:
+            import numpy as np
+            arrays["si"] = np.stack([gathered[pid]["si"] for pid in ids])
+            # TI of a PVS's first frame is undefined (NaN, no frame before it): left out
+            arrays["ti"] = np.stack([gathered[pid]["ti"][1:] for pid in ids])
+        dump_outputs(args.dump_outputs, arrays)
     bytes_pf = frame_bytes(sfmt, sw, sh) + frame_bytes(dfmt, dw, dh)
     achieved = bytes_pf * n / (scale_ms / 1000.0) / 1e9
     traffic = None
@@ -785,13 +868,13 @@ def main():
         if some is not None:
             out["siti_gather"] = {"pvs": len(gathered), "example": {"pvs": mine[0], "SI": round(some["SI"], 4),
                                                                    "TI": round(some["TI"], 4)}}
-    if world == 1 and not args.no_pipeline:
+    if args.full and world == 1 and not args.no_pipeline:
         out["pcie_pipeline"] = pcie_pipeline(wl, 600, dev)
-    if world == 1 and siti_wh and not args.no_siti_file:
+    if args.full and world == 1 and siti_wh and not args.no_siti_file:
         out["siti_file"] = siti_file(dev)
-    if world == 1 and args.workload == "config2" and not args.no_e2e:
+    if args.full and world == 1 and args.workload == "config2" and not args.no_e2e:
         out["e2e_avpvs"] = e2e_avpvs(wl, 600, dev, n_pvs=args.e2e_pvs, shared=args.e2e_encode == "shared")
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args, wl)
         ce = out["cpu_baseline"].get("e2e") if out["cpu_baseline"] else None
         if ce and out.get("e2e_avpvs") and ce.get("frames_per_s"):
@@ -852,6 +935,36 @@ def bench_stall(args, rank, world, dev):
                                        "passes of this workload), not measured in this run"}
     except (OSError, ValueError, KeyError):
         stall_traffic = None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"stall_" + k: a for k, a in sample_frames(dst).items()})
+    canvas = stall_canvas(args, rank, dev, dst) if args.full else None
+    if rank == 0:
+        print(json.dumps({"metric": "stall frames/s (config 4)", "value": round(world * n / (ms / 1000.0), 1),
+                          "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+                          "ms_per_step": round(ms, 4), "higher_is_better": True, "scaling": "weak",
+                          "vs_baseline": None, "dtype": "u16", "data": "synthetic",
+                          "config": {"workload": DESCR["config4"], "frames_per_launch": n},
+                          "roofline": {"bound": "hbm", "kernel": "stall_kernel", "achieved": round(achieved, 1),
+                                       "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
+                                       "traffic": stall_traffic["hbm_bytes"] if stall_traffic else None,
+                                       "traffic_detail": stall_traffic, "algorithmic_bytes_per_launch": 2 * fb * n,
+                                       "avg_launch_ms": round(ms, 4),
+                                       "note": "SURVEY 8d bytes (read + write per frame); the frozen frame is "
+                                               "read from HBM once per launch, so write_gbs is the HBM figure"},
+                          "write_gbs": round(write_gbs, 1), "write_frac_of_store_ceiling": round(write_gbs / 6774.0, 4),
+                          "write_frac_of_peak": round(write_gbs / HBM_PEAK_GBS, 4),
+                          "canvas_chain": canvas, "cpu_baseline": None, "library": library_id(),
+                          "tuning_overrides": tuning_overrides() or None}), flush=True)
+    return 0
+
+
+def stall_canvas(args, rank, dev, dst):
+    """--full, config 4: the canvas chain of a stall run, timed on its own."""
+    import torch
+    from pixpath import ops
+    from pixpath.frames import FrameBatch
+    w, h, n = dst.w, dst.h, dst.n
+    fb = frame_bytes("yuv422p10le", w, h)
     # the long test's canvases (create_avpvs_segment): 720p yuv420p10le segment
     # frames -> overlay yuv420p -> yuv422p10le 1080p, one chain-plan launch
     seg = FrameBatch("yuv420p10le", 1280, 720, n, device=dev)
@@ -877,24 +990,7 @@ def bench_stall(args, rank, world, dev):
               "algorithmic_bytes_per_launch": cbytes, "achieved": round(cbytes / (cms / 1000.0) / 1e9, 1),
               "frac": round(cbytes / (cms / 1000.0) / 1e9 / HBM_PEAK_GBS, 4),
               "note": "1280x720 yuv420p10le -> bicubic -> overlay yuv420p -> yuv422p10le 1920x1080"}
-    if rank == 0:
-        print(json.dumps({"metric": "stall frames/s (config 4)", "value": round(world * n / (ms / 1000.0), 1),
-                          "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-                          "ms_per_step": round(ms, 4), "higher_is_better": True, "scaling": "weak",
-                          "vs_baseline": None, "dtype": "u16", "data": "synthetic",
-                          "config": {"workload": DESCR["config4"], "frames_per_launch": n},
-                          "roofline": {"bound": "hbm", "kernel": "stall_kernel", "achieved": round(achieved, 1),
-                                       "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
-                                       "traffic": stall_traffic["hbm_bytes"] if stall_traffic else None,
-                                       "traffic_detail": stall_traffic, "algorithmic_bytes_per_launch": 2 * fb * n,
-                                       "avg_launch_ms": round(ms, 4),
-                                       "note": "SURVEY 8d bytes (read + write per frame); the frozen frame is "
-                                               "read from HBM once per launch, so write_gbs is the HBM figure"},
-                          "write_gbs": round(write_gbs, 1), "write_frac_of_store_ceiling": round(write_gbs / 6774.0, 4),
-                          "write_frac_of_peak": round(write_gbs / HBM_PEAK_GBS, 4),
-                          "canvas_chain": canvas, "cpu_baseline": None, "library": library_id(),
-                          "tuning_overrides": tuning_overrides() or None}), flush=True)
-    return 0
+    return canvas
 
 
 def bench_ffv1(args, rank, world, dev):
@@ -933,6 +1029,22 @@ def bench_ffv1(args, rank, world, dev):
     dt = (time.perf_counter() - t0) / args.steps
     dt = batch_barrier.max_over_ranks(dt, world)
     raw = frame_bytes("yuv422p10le", w, h)
+    head = {"metric": "FFV1 AVPVS encode frames/s (1080p yuv422p10le)", "value": round(world * n / dt, 1),
+            "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(dt * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "u16", "data": "synthetic (moving gradients + uniform noise in [-4, 4])",
+            "config": {"workload": "ffv1: FFV1 v3 intra encode of a 600-frame config-2 AVPVS", "frames": n,
+                       "slices": [nh, nv], "bytes_per_frame": round(float(sizes.mean()), 1),
+                       "compression": round(raw / float(sizes.mean()), 3)}}
+    if args.dump_outputs and rank == 0:
+        # the encoder's outputs: every packet size, and the first 4 MiB of the packet bytes
+        dump_outputs(args.dump_outputs, {"packet_sizes": np.asarray(sizes, np.float64),
+                                         "packet_bytes": buf.reshape(-1)[:4 << 20].cpu().numpy().astype(np.float32)})
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(dict(head, roofline=None, library=library_id(),
+                                  tuning_overrides=tuning_overrides() or None)), flush=True)
+        return 0
     # decode of the same packets (pinned host packets -> H2D -> one lane per
     # slice), as Ffv1AviReader hands them over (read into a pinned buffer)
     pk = buf.cpu().pin_memory().numpy()
@@ -1029,17 +1141,11 @@ def bench_ffv1(args, rank, world, dev):
                          "each: the AVPVS writer's lanes), best of %d; one_sub_batch_alone_s: one sub-batch with "
                          "the GPU to itself" % (n, K, max(1, args.steps))}
         del lencs, parts
-    out = {"metric": "FFV1 AVPVS encode frames/s (1080p yuv422p10le)", "value": round(world * n / dt, 1),
-           "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-           "ms_per_step": round(dt * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-           "dtype": "u16", "data": "synthetic (moving gradients + uniform noise in [-4, 4])",
-           "config": {"workload": "ffv1: FFV1 v3 intra encode of a 600-frame config-2 AVPVS", "frames": n,
-                      "slices": [nh, nv], "bytes_per_frame": round(float(sizes.mean()), 1),
-                      "compression": round(raw / float(sizes.mean()), 3)},
+    out = dict(head, **{
            "decode": {"frames_per_s": round(world * n / ddt, 1), "ms_per_step": round(ddt * 1e3, 3),
                       "lossless": lossless, "note": "packets from host memory (H2D included)"},
            "concurrent": conc, "writer_lanes": lanes,
-           "roofline": None, "library": library_id(), "tuning_overrides": tuning_overrides() or None}
+           "roofline": None, "library": library_id(), "tuning_overrides": tuning_overrides() or None})
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import ffv1_ref

@@ -6,13 +6,13 @@
 set -o pipefail
 TAG=$1
 export TMPDIR=/tmp
-mkdir -p gpurun_out
+mkdir -p ${OUT:-bench_out}
 ABL=$PWD/tools/ablate/libpixpath_ablate.so
 trace() {  # name lib [env ...]
   local v=$1 lib=$2; shift 2
-  env "$@" PIXPATH_LIB=$lib timeout -k 10 120 rocprofv3 --kernel-trace --output-format csv -d gpurun_out/kt_${v}_$TAG -o run -- python3 bench.py --allow-tuning --workload config4 --steps 6 --warmup 2 --no-cpu-baseline > gpurun_out/kt_${v}_$TAG.json 2> gpurun_out/kt_${v}_$TAG.err || { tail -3 gpurun_out/kt_${v}_$TAG.err; return 1; }
+  env "$@" PIXPATH_LIB=$lib timeout -k 10 120 rocprofv3 --kernel-trace --output-format csv -d ${OUT:-bench_out}/kt_${v}_$TAG -o run -- python3 bench.py --full --allow-tuning --workload config4 --steps 6 --warmup 2 --no-cpu-baseline > ${OUT:-bench_out}/kt_${v}_$TAG.json 2> ${OUT:-bench_out}/kt_${v}_$TAG.err || { tail -3 ${OUT:-bench_out}/kt_${v}_$TAG.err; return 1; }
   echo "== $v $*"
-  PIXPATH_TRACE_BY_GRID=1 python3 tools/trace_stats.py gpurun_out/kt_${v}_$TAG/run_kernel_trace.csv 2 strip_kernel | cut -d, -f1,3,4 | tail -n +2
+  PIXPATH_TRACE_BY_GRID=1 python3 tools/trace_stats.py ${OUT:-bench_out}/kt_${v}_$TAG/run_kernel_trace.csv 2 strip_kernel | cut -d, -f1,3,4 | tail -n +2
 }
 trace product $PWD/processing-chain_amd/pixpath/libpixpath.so || exit 1
 trace onelaunch $ABL PIXPATH_CHAIN_ONE_LAUNCH=1 || exit 1

@@ -3,10 +3,10 @@
 # Usage: bash tools/gpu_ffv1_pmc_r5.sh TAG
 set -o pipefail
 TAG=$1
-D=gpurun_out/fctr_$TAG
+D=${OUT:-bench_out}/fctr_$TAG
 mkdir -p $D
 export TMPDIR=/tmp
-RUN="python3 bench.py --workload ffv1 --steps 1 --warmup 0 --no-cpu-baseline --ffv1-concurrent 1"
+RUN="python3 bench.py --full --workload ffv1 --steps 1 --warmup 0 --no-cpu-baseline --ffv1-concurrent 1"
 i=0
 for set in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_LDS SQ_INSTS_VALU" \
            "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_VMEM SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAIT_INST_LDS" \

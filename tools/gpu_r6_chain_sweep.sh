@@ -1,13 +1,13 @@
 # Round 6: config-4 chain knob sweep on the measurement build (tools/ablate).  usage: bash tools/gpu_r6_chain_sweep.sh TAG
 set -o pipefail
 TAG=${1:-sw}
-mkdir -p gpurun_out
+mkdir -p ${OUT:-bench_out}
 export TMPDIR=/tmp
 ABL=$PWD/tools/var/libpixpath_abl.so
 one() {  # label env...
   local l=$1; shift
-  env "$@" PIXPATH_LIB=$ABL timeout -k 10 120 python3 bench.py --allow-tuning --workload config4 --steps 10 --warmup 2 --no-cpu-baseline > gpurun_out/sw_${TAG}_$l.json 2> gpurun_out/sw_${TAG}_$l.err || { tail -3 gpurun_out/sw_${TAG}_$l.err; return 1; }
-  python3 -c "import json;d=json.load(open('gpurun_out/sw_${TAG}_$l.json'));c=d['canvas_chain'];print('$l', c['avg_launch_ms'], c['frac'])"
+  env "$@" PIXPATH_LIB=$ABL timeout -k 10 120 python3 bench.py --full --allow-tuning --workload config4 --steps 10 --warmup 2 --no-cpu-baseline > ${OUT:-bench_out}/sw_${TAG}_$l.json 2> ${OUT:-bench_out}/sw_${TAG}_$l.err || { tail -3 ${OUT:-bench_out}/sw_${TAG}_$l.err; return 1; }
+  python3 -c "import json;d=json.load(open('${OUT:-bench_out}/sw_${TAG}_$l.json'));c=d['canvas_chain'];print('$l', c['avg_launch_ms'], c['frac'])"
 }
 for rep in 1 2 3; do
 one base X=1 || exit 1
