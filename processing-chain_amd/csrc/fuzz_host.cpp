@@ -16,7 +16,11 @@
 //   * the p02 bitstream scanners (scan.cpp pp_annexb_frame_sizes,
 //     pp_ivf_frame_sizes) on random and start-code-laden buffers;
 //   * the swscale filter construction (filters.cpp FilterBank::build /
-//     compact) for random sizes, flags and parameters.
+//     compact) for random sizes, flags and parameters;
+//   * the scaler planner (scale_plan.cpp): plain and chain layouts of the
+//     tested shapes and of seeded random ones, bound to their own table blob
+//     and walked the way scale_kernel / strip_kernel index them -- every
+//     window, ring row, staged row and LDS byte inside what the layout sizes.
 //
 //   * general FFV1 records given as seeds (file of u32-LE-length-prefixed
 //     records: the oracle's FFmpeg-like records with transmitted state
@@ -28,11 +32,14 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "ffv1host.hpp"
 #include "filters.hpp"
+#include "scale_plan.hpp"
 
 namespace pp {
 // the library's error sink (api.cpp in the product build)
@@ -275,6 +282,331 @@ long fuzz_filters(Rng &r, int iters) {
     return n;
 }
 
+// ---- scaler plans (scale_plan.cpp) ------------------------------------------
+// A layout bound to its own blob is walked as scale_kernel (scale.hip) and
+// strip_kernel (strip.hpp) walk it; every bound below is one of their unchecked
+// indexings.  `tag` names the plan in a failure message.
+#define PCHECK(cond, fmt, ...) CHECK(cond, "%s: " fmt, tag, ##__VA_ARGS__)
+
+using Taps = std::vector<std::pair<int, int>>;  // (source position, coefficient) of the non-zero taps
+
+size_t count32(const Table &t) { return t.off == Table::kNone ? 0 : t.bytes / 4; }
+
+Taps compact_taps(const FilterBank::Compact &c, int i) {
+    Taps t;
+    for (int k = 0; k < c.taps; ++k)
+        if (c.coef[(size_t)i * c.taps + k]) t.push_back({c.pos[i] + k, c.coef[(size_t)i * c.taps + k]});
+    return t;
+}
+
+// strip geometry and column windows (both kernels): the staged window of a
+// strip is 16-sample aligned, fits the staged row, and holds every H window
+void check_columns(const char *tag, const PlaneJob &J, const JobTables &T, int ht) {
+    PCHECK((1 << J.twl) == J.tw && J.tiles_x == (J.dw + J.tw - 1) / J.tw, "strips %d x %d for %d columns", J.tiles_x,
+           J.tw, J.dw);
+    PCHECK(count32(T.tile_c0) == (size_t)J.tiles_x && count32(T.tile_cn) == (size_t)J.tiles_x &&
+               count32(T.hpos) == (size_t)J.dw && T.hcoef.bytes == (size_t)J.dw * ht * 2,
+           "column table sizes");
+    PCHECK(J.S % 8 == 0, "staged row stride %d not 16-B", J.S);
+    for (int tx = 0; tx < J.tiles_x; ++tx) {
+        const int c0 = J.tile_c0[tx], cn = J.tile_cn[tx];
+        PCHECK(c0 >= 0 && c0 % 16 == 0 && cn % 16 == 0 && cn <= J.S, "strip %d window [%d, +%d) S %d", tx, c0, cn, J.S);
+        for (int x = tx * J.tw; x < std::min(J.dw, (tx + 1) * J.tw); ++x) {
+            const int pos = J.hpos[x];
+            PCHECK(pos >= c0 && pos + ht <= c0 + cn, "column %d window at %d outside [%d, +%d)", x, pos, c0, cn);
+            for (int k = 0; k < ht; ++k)
+                if (J.hcoef[(size_t)x * ht + k]) PCHECK(pos + k < J.sw, "column %d tap %d past the row", x, k);
+        }
+    }
+}
+
+// strip_kernel H tables: a lane reads HW dwords at hbase4 of the staged row and
+// its outputs' taps re-laid over them (hcoefw)
+void check_strip_h(const char *tag, const PlaneJob &F, const JobTables &T, int ht, int HW) {
+    const size_t ng = (size_t)F.tiles_x * (F.tw / 4);
+    PCHECK(count32(T.hbase4) == ng && count32(T.hcoefw) == ng * 4 * HW, "strip H table sizes");
+    for (size_t g = 0; g < ng; ++g) {
+        const int hb = F.hbase4[g];
+        PCHECK(hb >= 0 && hb % 4 == 0 && hb + 2 * HW <= F.S, "lane group %zu base %d + %d > S %d", g, hb, 2 * HW, F.S);
+    }
+    const int16_t *h16 = reinterpret_cast<const int16_t *>(F.hcoefw);
+    for (int x = 0; x < F.dw; ++x) {
+        const int c0 = F.tile_c0[x / F.tw], hb = F.hbase4[x / 4];
+        Taps got, want;
+        for (int s = 0; s < 2 * HW; ++s)
+            if (const int c = h16[(size_t)x * HW * 2 + s]) got.push_back({c0 + hb + s, c});
+        for (int k = 0; k < ht; ++k)
+            if (const int c = F.hcoef[(size_t)x * ht + k]) want.push_back({F.hpos[x] + k, c});
+        PCHECK(got == want, "column %d: re-laid taps differ from the compact filter", x);
+    }
+}
+
+// V tables and chunk rows: every row's window [base, base + 2 vtp) lies in the
+// ring of its chunk (window row 0 = the chunk's first source row, rounded to
+// even) and carries the compact V filter; strip_kernel reads vrow16 records
+void check_rows(const char *tag, const PlaneJob &J, const JobTables &T, const FilterBank::Compact &v, bool strip) {
+    const int nch = (J.dh + J.cho - 1) / J.cho;
+    PCHECK(J.cho > 0 && J.seg_h > 0 && J.seg_h % J.cho == 0, "segment %d rows, chunk %d", J.seg_h, J.cho);
+    PCHECK(count32(T.chunk_lo) == (size_t)nch && count32(T.chunk_hi) == (size_t)nch &&
+               count32(T.vbase) == (size_t)J.dh && count32(T.vcoef2) == (size_t)J.dh * J.vtp,
+           "row table sizes");
+    if (strip) PCHECK(J.vtp <= 8 && count32(T.vrow16) == (size_t)J.dh * 16, "strip row records, %d tap pairs", J.vtp);
+    PCHECK(J.ring % 2 == 0, "ring %d", J.ring);
+    for (int ci = 0; ci < nch; ++ci) {
+        const int lo = J.chunk_lo[ci], hi = J.chunk_hi[ci], b = lo & ~1;
+        PCHECK(0 <= lo && lo < hi && hi <= J.sh, "chunk %d rows [%d, %d) of %d", ci, lo, hi, J.sh);
+        PCHECK(hi - b <= J.ring, "chunk %d rows [%d, %d) past ring %d", ci, lo, hi, J.ring);
+        for (int y = ci * J.cho; y < std::min(J.dh, (ci + 1) * J.cho); ++y) {
+            const int32_t *rec = strip ? J.vrow16 + (size_t)y * 16 : nullptr;
+            const int base = strip ? rec[0] : J.vbase[y];
+            PCHECK(base % 2 == 0 && base >= b && base + 2 * J.vtp - b <= J.ring,
+                   "row %d window [%d, +%d) outside ring [%d, +%d)", y, base, 2 * J.vtp, b, J.ring);
+            Taps got;
+            for (int j = 0; j < J.vtp; ++j) {
+                const uint32_t w = (uint32_t)(strip ? rec[1 + j] : J.vcoef2[(size_t)y * J.vtp + j]);
+                if (const int c = (int16_t)(w & 0xffff)) got.push_back({base + 2 * j, c});
+                if (const int c = (int16_t)(w >> 16)) got.push_back({base + 2 * j + 1, c});
+            }
+            PCHECK(got == compact_taps(v, y), "row %d: tap pairs differ from the compact filter", y);
+            for (const auto &t : got) PCHECK(t.first >= lo && t.first < hi, "row %d reads unstaged row %d", y, t.first);
+        }
+    }
+}
+
+// the kernels' walk over the chunks of output rows [y_begin, y_end): the rows
+// new to each chunk fit the staging buffer (DIRECT stages none)
+void check_walk(const char *tag, const PlaneJob &J, int y_begin, int y_end, bool direct) {
+    const int nch = (J.dh + J.cho - 1) / J.cho;
+    PCHECK(y_begin >= 0 && y_begin % J.cho == 0 && y_begin < y_end && y_end <= J.dh, "walk [%d, %d) of %d rows", y_begin,
+           y_end, J.dh);
+    if (y_begin < 0 || y_begin >= J.dh) return;
+    int next = J.chunk_lo[y_begin / J.cho];
+    for (int y0 = y_begin; y0 < y_end; y0 += J.cho) {
+        const int ci = y0 / J.cho;
+        if (ci >= nch) break;  // (reported above: y_end > dh)
+        if (next < J.chunk_lo[ci]) next = J.chunk_lo[ci];
+        const int nnew = J.chunk_hi[ci] - next;
+        if (!direct) PCHECK(nnew <= J.maxnew, "chunk %d stages %d rows, buffer %d", ci, nnew, J.maxnew);
+        if (nnew > 0) next = J.chunk_hi[ci];
+    }
+}
+
+void check_segments(const char *tag, const PlaneJob &J, bool direct) {
+    PCHECK(J.tiles_y >= 1 && (J.tiles_y - 1) * J.seg_h < J.dh && J.tiles_y * J.seg_h >= J.dh, "%d segments of %d rows",
+           J.tiles_y, J.seg_h);
+    if (direct) PCHECK(J.maxnew == 0, "DIRECT with %d staged rows", J.maxnew);
+    for (int sg = 0; sg < J.tiles_y; ++sg) check_walk(tag, J, sg * J.seg_h, std::min(J.dh, (sg + 1) * J.seg_h), direct);
+}
+
+// fuse 2: the chroma planes of a fused chain layout.  Segments come from seg2;
+// after each first-stage chunk the second stage emits the rows chunk2 lists,
+// reading row pairs' windows from the circular byte ring2 (row & r2mask).
+void check_chain(const char *tag, const ScaleLayout &L, const PlaneJob &F, const JobTables &T) {
+    const int cdh1 = F.dh, dh2 = L.stage2->cdh, cho = F.cho, nch = (cdh1 + cho - 1) / cho, R = F.r2mask + 1;
+    const int npair = (dh2 + 1) / 2, VT2 = F.vtp2;
+    PCHECK(VT2 >= 1 && VT2 <= 3, "vtp2 %d", VT2);
+    PCHECK(R >= 2 && (R & (R - 1)) == 0, "ring2 of %d rows", R);
+    PCHECK(count32(T.vrow2) == (size_t)npair * 16 && count32(T.chunk2) == (size_t)nch * 4 &&
+               count32(T.seg2) == (size_t)F.tiles_y * 4 && F.tiles_y >= 1,
+           "second-stage table sizes");
+    FilterBank::Compact v2;
+    std::string err;
+    PCHECK(L.stage2->f[3].compact(cdh1, 1, &v2, &err) == 0, "second-stage filter: %s", err.c_str());
+    for (int m = 0; m < npair; ++m) {  // vrow2 records: base row, VT2 pairs of row 2m, VT2 of row 2m + 1
+        const int32_t *rec = F.vrow2 + (size_t)m * 16;
+        PCHECK(rec[0] >= 0 && rec[0] % 2 == 0, "pair %d base %d", m, rec[0]);
+        for (int h = 0; h < 2 && 2 * m + h < dh2; ++h) {
+            Taps got;
+            for (int j = 0; j < VT2; ++j) {
+                const uint32_t w = (uint32_t)rec[1 + h * VT2 + j];
+                if (const int c = (int16_t)(w & 0xffff)) got.push_back({rec[0] + 2 * j, c});
+                if (const int c = (int16_t)(w >> 16)) got.push_back({rec[0] + 2 * j + 1, c});
+            }
+            PCHECK(got == compact_taps(v2, 2 * m + h), "second-stage row %d: taps differ from the filter", 2 * m + h);
+        }
+    }
+    int done = 0;
+    for (int ci = 0; ci < nch; ++ci) {  // chunk2: monotone cover of [0, dh2)
+        const int32_t *c2 = F.chunk2 + 4 * ci;
+        PCHECK(c2[0] == done && c2[1] >= c2[0] && c2[1] <= dh2 && (c2[0] % 2 == 0 || c2[0] == dh2),
+               "chunk %d second-stage rows [%d, %d) after %d", ci, c2[0], c2[1], done);
+        done = c2[1];
+    }
+    PCHECK(done == dh2, "second-stage rows end at %d of %d", done, dh2);
+    int r_next = 0;
+    for (int sg = 0; sg < F.tiles_y; ++sg) {
+        const int32_t *s = F.seg2 + 4 * sg;
+        const int y_begin = s[0], y_end = s[1], r0 = s[2], r1 = s[3];
+        PCHECK(r0 == r_next && r0 < r1 && r0 % 2 == 0, "segment %d rows [%d, %d) after %d", sg, r0, r1, r_next);
+        r_next = r1;
+        PCHECK(y_begin >= 0 && y_begin % cho == 0 && (y_end % cho == 0 || y_end == cdh1) && y_end <= cdh1,
+               "segment %d first-stage rows [%d, %d) of %d", sg, y_begin, y_end, cdh1);
+        check_walk(tag, F, y_begin, y_end, false);
+        // the segment's walk: every row of [r0, r1) is emitted once, by a chunk
+        // that has every ring2 row its taps read (computed since y_begin, not
+        // yet overwritten: the ring holds rows (end - R, end))
+        int r = r0;
+        for (int y0 = y_begin; y0 < y_end && y0 / cho < nch; y0 += cho) {
+            const int32_t *c2 = F.chunk2 + 4 * (y0 / cho);
+            const int end = std::min(y_end, y0 + cho), b2 = c2[2];
+            const int lo2 = std::max(c2[0], r0), hi2 = std::min(c2[1], r1);
+            PCHECK(b2 % 2 == 0 && b2 <= y0 && end - b2 <= R, "chunk %d ring2 base %d, rows to %d, ring %d", y0 / cho, b2,
+                   end, R);
+            for (int q = lo2; q < hi2; ++q, ++r) {
+                PCHECK(q == r, "segment %d: row %d emitted at %d", sg, q, r);
+                const int pbase = F.vrow2[(size_t)(q / 2) * 16];
+                PCHECK(pbase >= b2 && pbase + 2 * VT2 <= b2 + R, "row %d window [%d, +%d) outside ring2 [%d, +%d)", q,
+                       pbase, 2 * VT2, b2, R);
+                for (const auto &t : compact_taps(v2, q))
+                    PCHECK(t.first >= y_begin && t.first < end && t.first >= end - R, "row %d tap row %d not in ring2 at %d",
+                           q, t.first, end);
+            }
+        }
+        PCHECK(r == r1, "segment %d emits rows to %d of %d", sg, r, r1);
+    }
+    PCHECK(r_next == dh2, "segments end at %d of %d", r_next, dh2);
+}
+
+// the LDS a strip_kernel launch of job F needs (strip.hpp: staged rows, window ring, ring2)
+size_t strip_lds(const PlaneJob &F) {
+    return (size_t)F.maxnew * F.S * 2 + (size_t)F.ring * F.tw * 2 + (F.fuse == 2 ? (size_t)(F.r2mask + 1) * F.tw : 0);
+}
+
+void check_layout(const char *tag, ScaleLayout &L) {
+    if (L.stage2) check_layout(tag, *L.stage2);
+    if (L.luma) {
+        check_layout(tag, *L.luma);
+        PCHECK(L.luma->fast_hw > 0 && strip_lds(L.luma->fjob[0]) == L.luma->fast_lds_plane[0], "luma launch LDS");
+    }
+    const ScaleLayout::Kind kind = L.kind == ScaleLayout::CHAIN ? L.first_kind : L.kind;
+    if (kind == ScaleLayout::COPY || kind == ScaleLayout::INTERLEAVE) {
+        PCHECK(L.blob.empty() && !L.chain_fused, "tables of an unscaled plan");
+        return;
+    }
+    bind(L, L.blob.data());
+    FilterBank::Compact v[2];
+    std::string err;
+    for (int c = 0; c < 2; ++c)
+        PCHECK(L.f[2 + c].compact(c ? L.csh : L.sh, 1, &v[c], &err) == 0, "vertical filter: %s", err.c_str());
+    // scale_kernel jobs (the fallback of every plan)
+    size_t lds = 0;
+    int base = 0;
+    for (int p = 0; p < 3; ++p) {
+        const PlaneJob &J = L.job[p];
+        check_columns(tag, J, L.jtab[p], L.ht);
+        check_rows(tag, J, L.jtab[p], v[p ? 1 : 0], false);
+        check_segments(tag, J, false);
+        PCHECK(J.tile_base == base, "plane %d tile base %d, running sum %d", p, J.tile_base, base);
+        base += J.tiles_x * J.tiles_y;
+        lds = std::max(lds, (size_t)J.maxnew * J.S * 2 + (size_t)J.ring * J.tw * 2 + (size_t)J.cho * J.vtp * 4 +
+                                (size_t)J.cho * 4);
+    }
+    PCHECK(lds == L.lds_bytes && lds <= (size_t)kLdsBudget, "scale_kernel LDS %zu, layout %zu", lds, L.lds_bytes);
+    if (!L.fast_hw) {
+        PCHECK(!L.direct && !L.chain_fused, "strip decisions without a strip plan");
+        return;
+    }
+    // strip_kernel jobs
+    lds = 0;
+    base = 0;
+    for (int p = 0; p < 3; ++p) {
+        const PlaneJob &F = L.fjob[p];
+        check_columns(tag, F, L.ftab[p], L.ht);
+        check_strip_h(tag, F, L.ftab[p], L.ht, L.fast_hw);
+        check_rows(tag, F, L.ftab[p], v[p ? 1 : 0], true);
+        if (F.fuse == 2) {
+            PCHECK(L.chain_fused && p > 0, "fuse 2 on plane %d", p);
+            if (L.chain_fused) check_chain(tag, L, F, L.ftab[p]);
+        } else {
+            check_segments(tag, F, L.direct);
+        }
+        // (a fused chain launch numbers its planes' tiles itself: fuse 2 changes tiles_y)
+        if (!L.chain_fused) PCHECK(F.tile_base == base, "strip plane %d tile base %d, running sum %d", p, F.tile_base, base);
+        base += F.tiles_x * F.tiles_y;
+        if (!(L.luma && p == 0)) lds = std::max(lds, strip_lds(F));  // (with `luma`, plane 0 runs from that layout)
+    }
+    if (L.chain_fused) {
+        PCHECK(lds <= L.chain_lds && L.chain_lds <= kChainLdsMax, "chain LDS %zu, needs %zu", L.chain_lds, lds);
+        if (L.luma) PCHECK(lds == L.chain_lds, "chroma launch LDS %zu, needs %zu", L.chain_lds, lds);
+    } else {
+        PCHECK(base == L.fast_tiles, "strip tiles %d, sum %d", L.fast_tiles, base);
+        PCHECK(lds == L.fast_lds && lds <= (size_t)kLdsBudget * (L.fast_tw / 256), "strip LDS %zu, layout %zu", lds,
+               L.fast_lds);
+    }
+}
+
+struct PlanCase {
+    bool chain;
+    int sf, sw, sh, df, dw, dh, flags;
+};
+
+void plan_case(const PlanCase &c) {
+    char tag[96];
+    std::snprintf(tag, sizeof tag, "%s %d %dx%d -> %d %dx%d flags 0x%x", c.chain ? "chain" : "plan", c.sf, c.sw, c.sh,
+                  c.df, c.dw, c.dh, c.flags);
+    std::unique_ptr<ScaleLayout> L;
+    const int rc = c.chain ? plan_chain_layout(c.sf, c.sw, c.sh, c.df, c.dw, c.dh, c.flags, PP_SWS_PARAM_DEFAULT,
+                                               PP_SWS_PARAM_DEFAULT, &L)
+                           : plan_layout(c.sf, c.sw, c.sh, c.df, c.dw, c.dh, c.flags, PP_SWS_PARAM_DEFAULT,
+                                         PP_SWS_PARAM_DEFAULT, &L);
+    PCHECK((rc == 0) == (L != nullptr) && rc <= 0, "return code %d %s a layout", rc, L ? "with" : "without");
+    if (L) check_layout(tag, *L);
+}
+
+long fuzz_plans(Rng &r, int iters) {
+    static const PlanCase fixed[] = {
+        // tests/test_native_abi.py CONFIGS and chain cases, the 6x shapes of tests/test_gpu_scale.py
+        {false, PP_FMT_YUV420P, 1280, 720, PP_FMT_YUV420P, 1920, 1080, PP_SWS_BICUBIC},
+        {false, PP_FMT_YUV422P10LE, 1280, 720, PP_FMT_YUV422P10LE, 1920, 1080, PP_SWS_BICUBIC},
+        {false, PP_FMT_YUV422P10LE, 1280, 720, PP_FMT_YUV422P10LE, 1920, 1080, PP_SWS_LANCZOS},
+        {false, PP_FMT_YUV420P10LE, 960, 540, PP_FMT_YUV420P, 1920, 1080, PP_SWS_BICUBIC},
+        {false, PP_FMT_YUV420P, 1920, 1080, PP_FMT_YUV422P10LE, 1920, 1080, PP_SWS_BICUBIC},
+        {false, PP_FMT_YUV420P, 1920, 1080, PP_FMT_YUV420P, 1280, 720, PP_SWS_BICUBIC},
+        {false, PP_FMT_YUV422P10LE, 3840, 2160, PP_FMT_YUV422P10LE, 1920, 1080, PP_SWS_BICUBIC},
+        {false, PP_FMT_YUV420P, 3840, 2160, PP_FMT_YUV422P10LE, 1920, 1080, PP_SWS_BICUBIC},
+        {false, PP_FMT_YUV420P, 3840, 2160, PP_FMT_YUV420P, 640, 360, PP_SWS_BICUBIC},
+        {false, PP_FMT_YUV420P, 3840, 1600, PP_FMT_YUV420P, 1920, 800, PP_SWS_BICUBIC},
+        {false, PP_FMT_YUV420P, 4096, 2160, PP_FMT_YUV420P, 1920, 1012, PP_SWS_LANCZOS},
+        {false, PP_FMT_YUV420P, 640, 360, PP_FMT_YUV420P, 3840, 2160, PP_SWS_BICUBIC},
+        {false, PP_FMT_YUV422P, 250, 99, PP_FMT_YUV420P10LE, 77, 61, PP_SWS_LANCZOS},
+        {false, PP_FMT_YUV444P10LE, 64, 48, PP_FMT_YUV422P, 130, 90, PP_SWS_BICUBIC},
+        {false, PP_FMT_YUV420P, 333, 197, PP_FMT_YUV420P, 500, 301, PP_SWS_BILINEAR},
+        {false, PP_FMT_YUV420P, 1920, 1080, PP_FMT_UYVY422, 1920, 1080, PP_SWS_BICUBIC},
+        {false, PP_FMT_YUV420P, 8, 8, PP_FMT_YUV420P, 3, 3, PP_SWS_BICUBIC},
+        {true, PP_FMT_YUV420P10LE, 1280, 720, PP_FMT_YUV422P10LE, 1920, 1080, PP_SWS_BICUBIC},
+        {true, PP_FMT_YUV422P10LE, 1280, 720, PP_FMT_YUV422P10LE, 1920, 1080, PP_SWS_BICUBIC},
+        {true, PP_FMT_YUV420P, 1280, 720, PP_FMT_YUV422P, 1920, 1080, PP_SWS_BICUBIC},
+        {true, PP_FMT_YUV420P, 1280, 720, PP_FMT_YUV420P10LE, 1920, 1080, PP_SWS_BICUBIC},
+        {true, PP_FMT_YUV420P, 1920, 1080, PP_FMT_YUV422P10LE, 1920, 1080, PP_SWS_BICUBIC},
+        // refused: packed source, packed chain target, too small, no filter
+        {false, PP_FMT_UYVY422, 64, 64, PP_FMT_YUV420P, 32, 32, PP_SWS_BICUBIC},
+        {true, PP_FMT_YUV420P, 64, 64, PP_FMT_UYVY422, 64, 64, PP_SWS_BICUBIC},
+        {false, PP_FMT_YUV420P, 3, 64, PP_FMT_YUV420P, 32, 32, PP_SWS_BICUBIC},
+        {false, PP_FMT_YUV420P, 64, 64, PP_FMT_YUV420P, 32, 32, 0},
+    };
+    long n = 0;
+    for (const PlanCase &c : fixed) {
+        plan_case(c);
+        ++n;
+    }
+    // seeded plans: a third chain plans, every filter, every planar format
+    // pair; ragged sizes in 4..700, now and then one very small side
+    static const int flags[] = {PP_SWS_BICUBIC, PP_SWS_LANCZOS, PP_SWS_BILINEAR};
+    static const int targets[] = {PP_FMT_YUV422P, PP_FMT_YUV420P10LE, PP_FMT_YUV422P10LE, PP_FMT_YUV420P};
+    auto side = [&r] { return r.below(8) ? 4 + r.below(697) : 4 + r.below(5); };
+    for (int it = 0; it < iters; ++it) {
+        PlanCase c;
+        c.chain = it % 3 == 2;
+        c.sf = (it / 3) % 6;  // the six planar formats (PP_FMT_YUV420P .. PP_FMT_YUV444P10LE)
+        c.df = c.chain ? targets[(it / 18) % 4] : (it / 18) % 6;
+        c.flags = flags[r.below(3)];
+        c.sw = side(); c.sh = side(); c.dw = side(); c.dh = side();
+        plan_case(c);
+        ++n;
+    }
+    return n;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -286,6 +618,8 @@ int main(int argc, char **argv) {
     const long c = fuzz_scanners(r, iters / 4);
     const long d = fuzz_filters(r, iters / 20);
     const long e = argc > 3 ? fuzz_seed_records(r, iters, argv[3]) : 0;
-    std::printf("records %ld packets %ld scans %ld filters %ld seeded %ld failures %d\n", a, b, c, d, e, g_fail);
+    const long f = fuzz_plans(r, iters / 60);
+    std::printf("records %ld packets %ld scans %ld filters %ld seeded %ld plans %ld failures %d\n", a, b, c, d, e, f,
+                g_fail);
     return g_fail ? 1 : 0;
 }

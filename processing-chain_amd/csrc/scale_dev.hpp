@@ -1,7 +1,8 @@
 // Device-side pieces shared by the scaler kernels (scale.hip: general
 // scale_kernel, strip_u16.hip / strip_u8.hip: strip_kernel instances): plane
-// jobs, launch arguments, ordered-dither matrix, 16-B buffer loads, v_dot2
-// helpers and LDS staging stores.  See scale.hip for the reference semantics.
+// jobs and launch arguments (scale_plan.hpp, shared with the host planner),
+// ordered-dither matrix, 16-B buffer loads, v_dot2 helpers and LDS staging
+// stores.  See scale.hip for the reference semantics.
 #pragma once
 #include <algorithm>
 #include <climits>
@@ -11,20 +12,9 @@
 
 #include "common.hpp"
 #include "device.hpp"
+#include "scale_plan.hpp"
 
 namespace pp {
-
-constexpr int kTileW = 256;      // widest output tile (columns); narrower for large downscales
-constexpr int kThreads = 256;    // 4 waves
-constexpr int kLdsBudget = 40 * 1024;
-#ifndef PIXPATH_CHO_MAX
-#define PIXPATH_CHO_MAX 32
-#endif
-#ifndef PIXPATH_SEG_ROWS
-#define PIXPATH_SEG_ROWS 540
-#endif
-constexpr int kChoMax = PIXPATH_CHO_MAX;    // output rows per chunk (upper bound)
-constexpr int kSegRows = PIXPATH_SEG_ROWS;  // output rows per segment (target; profiles/r2: 540 beats 256 by ~1.5 %)
 
 static __constant__ uint8_t c_dither[8][8] = {
     {36, 68, 60, 92, 34, 66, 58, 90},  {100, 4, 124, 28, 98, 2, 122, 26},
@@ -49,48 +39,6 @@ constexpr uint8_t kDither[8][8] = {
 static __constant__ uint64_t c_dither64[8] = {
     dither_row64(kDither[0]), dither_row64(kDither[1]), dither_row64(kDither[2]), dither_row64(kDither[3]),
     dither_row64(kDither[4]), dither_row64(kDither[5]), dither_row64(kDither[6]), dither_row64(kDither[7]),
-};
-
-struct PlaneJob {
-    int sw, sh, dw, dh;
-    int tiles_x, tiles_y, tile_base;  // strips x vertical segments, first block index
-    int tw, twl, seg_h, cho; // strip width (= 1 << twl), output rows per segment, output rows per chunk
-    int vtp, ring, maxnew, S; // V tap pairs, window rows (even), staged rows per chunk, staged cols
-    int dither_off;       // 0 (Y, U) or 3 (V)
-    const int32_t *hpos;  // [dw]   window start (absolute source column)
-    const int16_t *hcoef; // [dw * HT]
-    const int32_t *vbase; // [dh]   first ring row of the window, rounded down to even
-    const int32_t *vcoef2; // [dh * vtp] tap pairs (rows base+2j, base+2j+1) packed lo|hi
-    const int32_t *tile_c0, *tile_cn; // [tiles_x] staged column window per strip
-    const int32_t *chunk_lo, *chunk_hi; // [ceil(dh/cho)] source rows needed by each chunk
-    // strip_kernel only
-    const int32_t *hbase4;  // [tiles_x * 64] 8-B aligned window base (staged-row sample) per 4-column lane
-    const int32_t *hcoefw;  // [tiles_x * 64][4][HW] taps re-laid over the lane's HW dwords (int16 pairs)
-    const int32_t *vrow16;  // [dh][16] per output row: window base row (even), then 8 tap pairs (zero padded)
-    // chain plans (strip_kernel FUSE != 0, see strip.hpp)
-    int fuse;               // 0 as is, 1 identity second stage, 2 second-stage vertical filter through ring2
-    int vtp2;               // second-stage V tap pairs (fuse 2)
-    int r2mask;             // fuse 2: rows of the circular byte ring2 - 1 (a power of two)
-    const int32_t *vrow2;   // [dh2][16] second-stage row records (base row, tap pairs)
-    const int32_t *chunk2;  // [nch][4] per chunk: second-stage rows [lo2, hi2), ring2 base row, kept pairs
-    const int32_t *seg2;    // fuse 2: [tiles_y][4] per segment: first-stage rows [y0, y1) (chunk aligned,
-                            // overlapping by the second stage's halo), second-stage rows [r0, r1) it stores
-    int pk_off, pk_step;    // strip_kernel FUSE == 1: byte offset / step of this plane in the uyvy422 row
-};
-
-struct ScaleArgs {
-    PlaneJob pl[3];
-    const uint8_t *src[3];
-    int64_t sls[3], sfs[3];
-    uint8_t *dst[3];
-    int64_t dls[3], dfs[3];
-    int nplanes;
-    int tiles;    // workgroups per frame (all planes)
-    int hshift;   // 7 for 8-bit sources, depth-1 otherwise
-    int dither;   // ordered dither (>8-bit source narrowed to 8 bit)
-    int vec_src;  // all source rows 16-B aligned
-    int vec_dst;  // all destination rows 8-B aligned (4 outputs per lane)
-    int debug;    // ablation (measurement only, PIXPATH_SCALE_DEBUG): 1 no V stores, 2 no staging loads, 4 no H pass
 };
 
 // Register prefetch of up to kPF 16-byte source chunks per lane (software

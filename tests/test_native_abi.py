@@ -140,3 +140,48 @@ def test_chain_plan_host_only(sf, sw, sh, df, dw, dh, fused):
         L.pp_scale_plan_destroy(h)
     assert L.pp_scale_chain_plan_create(None, 0, 64, 64, po.FMT_BY_NAME["uyvy422"], 64, 64, 4, 1.0, 1.0,
                                         ctypes.byref(h)) == -1
+
+
+# (chain plan, source, size, target, size, flags) -> (pp_scale_plan_path, the ten pp_scale_plan_stats values:
+# lds_bytes, threads, tiles_per_frame, cho, seg_rows, vtp_luma, vtp_chroma, staged_cols, window_rows, max_new_rows),
+# recorded from the library before the planner moved out of scale.hip
+PINNED_GEOMETRY = [
+    ((False, 'yuv420p', 1280, 720, 'yuv420p', 1920, 1080, 4), (4, (23936, 256, 24, 32, 544, 3, 3, 192, 28, 25))),
+    ((False, 'yuv422p10le', 1280, 720, 'yuv422p10le', 1920, 1080, 4), (4, (23936, 256, 32, 32, 544, 3, 3, 192, 28, 25))),
+    ((False, 'yuv422p10le', 1280, 720, 'yuv422p10le', 1920, 1080, 512), (6, (25728, 256, 32, 32, 544, 4, 4, 192, 30, 27))),
+    ((False, 'yuv420p10le', 960, 540, 'yuv420p', 1920, 1080, 4), (4, (17664, 256, 24, 32, 544, 3, 3, 160, 22, 20))),
+    ((False, 'yuv420p', 1920, 1080, 'yuv422p10le', 1920, 1080, 4), (3, (33792, 256, 32, 32, 544, 1, 3, 272, 32, 32))),
+    ((False, 'yuv420p', 1920, 1080, 'yuv420p', 1280, 720, 4), (6, (36992, 256, 11, 16, 720, 4, 4, 416, 30, 26))),
+    ((False, 'yuv422p10le', 3840, 2160, 'yuv422p10le', 1920, 1080, 4), (8, (36224, 256, 32, 8, 544, 5, 5, 544, 24, 22))),
+    ((False, 'yuv420p', 3840, 2160, 'yuv420p', 640, 360, 4), (0, (33312, 256, 20, 4, 360, 13, 13, 416, 44, 33))),
+    ((False, 'yuv420p', 3840, 1600, 'yuv420p', 1920, 800, 4), (8, (28672, 256, 16, 24, 816, 5, 5, 544, 56, 0))),
+    ((False, 'yuv420p', 4096, 2160, 'yuv420p', 1920, 1012, 512), (12, (34304, 256, 24, 4, 508, 7, 7, 576, 22, 20))),
+    ((False, 'yuv420p', 640, 360, 'yuv420p', 3840, 2160, 4), (4, (7424, 256, 92, 32, 544, 3, 3, 64, 12, 10))),
+    ((False, 'yuv422p', 250, 99, 'yuv420p10le', 77, 61, 512), (0, (39552, 256, 3, 24, 72, 6, 10, 256, 50, 43))),
+    ((False, 'yuv444p10le', 64, 48, 'yuv422p', 130, 90, 4), (0, (15232, 256, 3, 32, 96, 3, 3, 64, 24, 19))),
+    ((False, 'yuv420p', 333, 197, 'yuv420p', 500, 301, 2), (4, (21056, 256, 4, 32, 320, 2, 2, 176, 26, 22))),
+    ((False, 'yuv420p', 1920, 1080, 'uyvy422', 1920, 1080, 4), (3, (33792, 256, 32, 32, 544, 1, 3, 272, 32, 32))),
+    ((True, 'yuv420p10le', 1280, 720, 'yuv422p10le', 1920, 1080, 4), (4, (21760, 256, 24, 16, 544, 3, 3, 192, 16, 14))),
+    ((True, 'yuv422p10le', 1280, 720, 'yuv422p10le', 1920, 1080, 4), (4, (32512, 256, 24, 16, 544, 3, 4, 192, 16, 14))),
+    ((True, 'yuv420p', 1280, 720, 'yuv422p', 1920, 1080, 4), (4, (21760, 256, 24, 16, 544, 3, 3, 192, 16, 14))),
+    ((True, 'yuv420p', 1280, 720, 'yuv420p10le', 1920, 1080, 4), (4, (13568, 256, 24, 16, 544, 3, 3, 192, 16, 14))),
+    ((True, 'yuv420p', 1920, 1080, 'yuv422p10le', 1920, 1080, 4), (0, (0, 256, 0, 0, 0, 0, 0, 0, 0, 0))),
+]
+
+
+def test_plan_geometry_pinned():
+    """The planner's decisions (strip / chain path, LDS, tiles, chunk and ring
+    geometry) for every CONFIGS entry and every chain case, as host-only plans."""
+    L = _native.lib()
+    assert [c for ch, *c in (k for k, _ in PINNED_GEOMETRY) if not ch] == [list(c) for c in CONFIGS]
+    for (is_chain, sf, sw, sh, df, dw, dh, fl), (path, stats) in PINNED_GEOMETRY:
+        h = ctypes.c_void_p()
+        create = L.pp_scale_chain_plan_create if is_chain else L.pp_scale_plan_create
+        _native.check(create(None, po.FMT_BY_NAME[sf], sw, sh, po.FMT_BY_NAME[df], dw, dh, fl, ops.PARAM_DEFAULT,
+                             ops.PARAM_DEFAULT, ctypes.byref(h)))
+        try:
+            v = np.zeros(10, np.int64)
+            n = _native.check(L.pp_scale_plan_stats(h, v.ctypes.data, 10))
+            assert (L.pp_scale_plan_path(h), tuple(int(x) for x in v[:n])) == (path, stats), (sf, sw, sh, df, dw, dh)
+        finally:
+            L.pp_scale_plan_destroy(h)
