@@ -42,11 +42,10 @@
 
 #include "common.hpp"
 #include "device.hpp"
+#include "ffv1_dev.hpp"
 #include "ffv1host.hpp"
 
 namespace pp {
-
-constexpr int kCtxSize = kFfv1CtxBytes;  // state bytes per context
 
 // ---- device ---------------------------------------------------------------
 struct Ffv1Args {
@@ -59,7 +58,7 @@ struct Ffv1Args {
     int nctx;               // contexts of the record's set (Ffv1Quant::contexts)
     int64_t *sizes;         // [nslices] coded bytes, -1 = overflow
     uint32_t *crcs;         // [nslices] CRC-32 of the coded bytes
-    const uint8_t *tables;  // zero[256], one[256], crc table (1 KB)
+    const uint8_t *tables;  // the table blob (ffv1_dev.hpp) up to the crc table
     uint32_t *tok;          // [nslices / 64][tok_len][64] tokens
     int64_t tok_len;        // tokens per slice, max over the grid
     uint32_t *raw;          // [nslices][raw_cap] renorm records, two per dword; ffv1_resolve_kernel
@@ -73,106 +72,6 @@ struct Ffv1Args {
     int qthr[5];            // the record's quantiser (Ffv1Quant): thresholds, unused ones 1024
     int qL;                 // its levels: context = q(L - TL) + qL q(TL - T) + qL^2 q(T - TR)
 };
-
-// ffv1_quant (ffv1host.cpp) on the device: the number of thresholds <= |d|
-__device__ inline int dquant(int d, const int (&thr)[5]) {  // d already & 0xFF
-    const int m = d < 128 ? d : (d == 128 ? 127 : 256 - d);
-    const int q = (m >= thr[0]) + (m >= thr[1]) + (m >= thr[2]) + (m >= thr[3]) + (m >= thr[4]);
-    return d < 128 ? q : -q;
-}
-
-__device__ inline int median3(int a, int b, int c) {
-    return max(min(a, b), min(max(a, b), c));
-}
-
-// The slice's range coder (rangecoder.c put_rac / renorm_encoder) and
-// put_symbol; every method force-inlined so the coder lives in registers.
-struct DevRC {
-    int low, range, oc, ob;
-    uint8_t *p, *end;
-    uint32_t crc;
-    bool over;
-    const uint8_t *zero, *one;
-    const uint32_t *crc_tab;
-
-    __device__ __forceinline__ void emit(int v) {
-        if (p < end) {
-            *p++ = (uint8_t)v;
-            crc = (crc << 8) ^ crc_tab[(crc >> 24) ^ (uint32_t)(v & 0xFF)];
-        } else {
-            over = true;
-        }
-    }
-    __device__ __forceinline__ void renorm() {
-        while (range < 0x100) {
-            if (ob < 0) {
-                ob = low >> 8;
-            } else if (low <= 0xFF00) {
-                emit(ob);
-                for (; oc; oc--) emit(0xFF);
-                ob = low >> 8;
-            } else if (low >= 0x10000) {
-                emit(ob + 1);
-                for (; oc; oc--) emit(0x00);
-                ob = (low >> 8) - 0x100;
-            } else {
-                oc++;
-            }
-            low = (low & 0xFF) << 8;
-            range <<= 8;
-        }
-    }
-    // one binary decision with the adaptive state byte at *st (HBM/L2)
-    __device__ __forceinline__ void rac(uint8_t *st, int bit) {
-        const int sv = *st;
-        const int r1 = (range * sv) >> 8;
-        if (!bit) {
-            range -= r1;
-            *st = zero[sv];
-        } else {
-            low += range - r1;
-            range = r1;
-            *st = one[sv];
-        }
-        renorm();
-    }
-    __device__ __forceinline__ void symbol(uint8_t *st, int v, bool is_signed) {
-        if (!v) {
-            rac(st, 1);
-            return;
-        }
-        const int av = v < 0 ? -v : v;
-        const int e = 31 - __clz(av);
-        rac(st, 0);
-        for (int i = 0; i < e; i++) rac(st + 1 + min(i, 9), 1);
-        rac(st + 1 + min(e, 9), 0);
-        for (int i = e - 1; i >= 0; i--) rac(st + 22 + min(i, 9), (av >> i) & 1);
-        if (is_signed) rac(st + 11 + min(e, 10), v < 0);
-    }
-};
-
-// ---- slice geometry (RFC 9043 4.6: slice_x .. in units of the grid) ---------
-struct SliceGeo {
-    int frame, s, sx, sy, x0, x1, y0, y1, lw, lh, cw, ch;
-    __device__ __host__ int len() const { return lw * lh + 2 * cw * ch; }
-};
-__device__ __host__ inline SliceGeo slice_geo(int g, int w, int h, int nh, int nv, int hsub, int vsub) {
-    SliceGeo q;
-    const int per = nh * nv;
-    q.frame = g / per;
-    q.s = g - q.frame * per;
-    q.sy = q.s / nh;
-    q.sx = q.s - q.sy * nh;
-    q.x0 = (int)((int64_t)q.sx * w / nh);
-    q.x1 = (int)((int64_t)(q.sx + 1) * w / nh);
-    q.y0 = (int)((int64_t)q.sy * h / nv);
-    q.y1 = (int)((int64_t)(q.sy + 1) * h / nv);
-    q.lw = q.x1 - q.x0;
-    q.lh = q.y1 - q.y0;
-    q.cw = (q.lw + (1 << hsub) - 1) >> hsub;
-    q.ch = (q.lh + (1 << vsub) - 1) >> vsub;
-    return q;
-}
 
 // ---- 1. modelling: tokens (context key << 16 | folded residual) -------------
 // One workgroup of 256 threads per (64-slice wave group, plane row).  A token
@@ -351,19 +250,14 @@ __device__ __forceinline__ void enc_renorm(Enc &c) {
     }
 }
 
-// state byte k of a 32-byte block held in 8 dwords (k a compile-time constant
-// after unrolling: no dynamic register indexing)
-__device__ __forceinline__ uint32_t sget(const uint32_t (&b)[8], int k) { return (b[k >> 2] >> ((k & 3) * 8)) & 0xFFu; }
-__device__ __forceinline__ void sput(uint32_t (&b)[8], int k, uint32_t v) {
-    b[k >> 2] = (b[k >> 2] & ~(0xFFu << ((k & 3) * 8))) | (v << ((k & 3) * 8));
-}
-// runtime index k in 8..23 (the sign state 11 + e), branch-free selects
-__device__ __forceinline__ uint32_t sget_dyn(const uint32_t (&b)[8], int k) {
+// state byte k of an 8-dword block at a runtime index k in 8..23 (the sign
+// state 11 + e), branch-free selects
+__device__ __forceinline__ uint32_t enc_get_dyn(const uint32_t (&b)[8], int k) {
     const int w = k >> 2;
     const uint32_t lo = (w & 1) ? b[3] : b[2], hi = (w & 1) ? b[5] : b[4];
     return __builtin_amdgcn_ubfe(w >= 4 ? hi : lo, (k & 3) * 8, 8);
 }
-__device__ __forceinline__ void sput_dyn(uint32_t (&b)[8], int k, uint32_t v, bool on) {
+__device__ __forceinline__ void enc_put_dyn(uint32_t (&b)[8], int k, uint32_t v, bool on) {
     const int w = k >> 2;
     const uint32_t sh = (k & 3) * 8, m = ~(0xFFu << sh), nv = v << sh;
     b[2] = on && w == 2 ? (b[2] & m) | nv : b[2];
@@ -393,23 +287,23 @@ __device__ __forceinline__ void enc_symbol(Enc &c, uint32_t (&b)[8], int v, cons
     const bool nz = v != 0;
     const int e = nz ? 31 - __clz(a) : -1;
     const int E = wave_max_e(e);
-    const uint32_t s0 = sget(b, 0);
+    const uint32_t s0 = st_get(b, 0);
     uint32_t su[10], sm[9], ss = 0, n0, nu[10], nm[9], nsg = 0;
     n0 = tab[s0 | (nz ? 0u : 256u)];
 #pragma unroll
     for (int i = 0; i < 10; ++i)
         if (i <= E) {
-            su[i] = sget(b, 1 + i);
+            su[i] = st_get(b, 1 + i);
             nu[i] = tab[su[i] | (i < e ? 256u : 0u)];
         }
 #pragma unroll
     for (int i = 0; i < 9; ++i)
         if (i < E) {
-            sm[i] = sget(b, 22 + i);
+            sm[i] = st_get(b, 22 + i);
             nm[i] = tab[sm[i] | (((a >> i) & 1u) << 8)];
         }
     if (SIGNED && E >= 0) {
-        ss = sget_dyn(b, 11 + (e < 0 ? 0 : e));
+        ss = enc_get_dyn(b, 11 + (e < 0 ? 0 : e));
         nsg = tab[ss | (v < 0 ? 256u : 0u)];
     }
     enc_dec(c, s0, !nz);
@@ -420,28 +314,18 @@ __device__ __forceinline__ void enc_symbol(Enc &c, uint32_t (&b)[8], int v, cons
     for (int i = 8; i >= 0; --i)
         if (i < E) enc_dec(c, i < e ? sm[i] : 0u, i < e && ((a >> i) & 1u));
     if (SIGNED && E >= 0) enc_dec(c, nz ? ss : 0u, v < 0);
-    sput(b, 0, n0);
+    st_put(b, 0, n0);
 #pragma unroll
     for (int i = 0; i < 10; ++i)
-        if (i <= E) sput(b, 1 + i, i <= e ? nu[i] : su[i]);
+        if (i <= E) st_put(b, 1 + i, i <= e ? nu[i] : su[i]);
 #pragma unroll
     for (int i = 0; i < 9; ++i)
-        if (i < E) sput(b, 22 + i, i < e ? nm[i] : sm[i]);
-    if (SIGNED && E >= 0) sput_dyn(b, 11 + (e < 0 ? 0 : e), nsg, nz);
+        if (i < E) st_put(b, 22 + i, i < e ? nm[i] : sm[i]);
+    if (SIGNED && E >= 0) enc_put_dyn(b, 11 + (e < 0 ? 0 : e), nsg, nz);
 }
 
-// A context's 32 state bytes split in two 16-byte halves (the decoder's
-// layout, ffv1dec.hip).  HOT, the block the coder forwards and prefetches:
-// [0] zero flag, [1..5] exponent bits 0..4, [6..10] sign for e = 0..4,
-// [11..14] mantissa bits 0..3 -- every state a residual below 32 touches.
-// COLD, read and written in place only while the wave's longest exponent is
-// >= 5: [0..4] exponent bits 5..9, [5..9] sign for e = 5..9, [10..14]
-// mantissa bits 4..8.
-__device__ __forceinline__ uint32_t hget(const uint32_t (&b)[4], int k) { return (b[k >> 2] >> ((k & 3) * 8)) & 0xFFu; }
-__device__ __forceinline__ void hput(uint32_t (&b)[4], int k, uint32_t v) {
-    b[k >> 2] = (b[k >> 2] & ~(0xFFu << ((k & 3) * 8))) | (v << ((k & 3) * 8));
-}
-// enc_symbol on the split block: the same decisions in the same order
+// enc_symbol on the split block (HOT in `b`, COLD at `cold`: ffv1_dev.hpp): the
+// same decisions in the same order
 template <bool SIGNED>
 __device__ __forceinline__ void enc_symbol_split(Enc &c, uint32_t (&b)[4], uint8_t *cold, int v, const uint8_t *tab) {
     const uint32_t a = (uint32_t)(v < 0 ? -v : v);
@@ -450,28 +334,27 @@ __device__ __forceinline__ void enc_symbol_split(Enc &c, uint32_t (&b)[4], uint8
     const int E = wave_max_e(e);
     uint32_t cb[4] = {0u, 0u, 0u, 0u};
     if (E >= 5) {  // wave-uniform
-        const uint4 x = *reinterpret_cast<const uint4 *>(cold);
-        cb[0] = x.x; cb[1] = x.y; cb[2] = x.z; cb[3] = x.w;
+        hblk_load(cb, cold);
     }
-    const uint32_t s0 = hget(b, 0);
+    const uint32_t s0 = st_get(b, 0);
     uint32_t su[10], sm[9], ss = 0, n0, nu[10], nm[9], nsg = 0;
     n0 = tab[s0 | (nz ? 0u : 256u)];
 #pragma unroll
     for (int i = 0; i < 10; ++i)
         if (i <= E) {
-            su[i] = i < 5 ? hget(b, 1 + i) : hget(cb, i - 5);
+            su[i] = i < 5 ? st_get(b, 1 + i) : st_get(cb, i - 5);
             nu[i] = tab[su[i] | (i < e ? 256u : 0u)];
         }
 #pragma unroll
     for (int i = 0; i < 9; ++i)
         if (i < E) {
-            sm[i] = i < 4 ? hget(b, 11 + i) : hget(cb, 10 + i - 4);
+            sm[i] = i < 4 ? st_get(b, 11 + i) : st_get(cb, 10 + i - 4);
             nm[i] = tab[sm[i] | (((a >> i) & 1u) << 8)];
         }
     const int es = e < 0 ? 0 : e;
     if (SIGNED && E >= 0) {  // sign state of exponent es: compile-time byte indices under selects
 #pragma unroll
-        for (int i = 0; i < 10; ++i) ss = es == i ? (i < 5 ? hget(b, 6 + i) : hget(cb, i)) : ss;
+        for (int i = 0; i < 10; ++i) ss = es == i ? (i < 5 ? st_get(b, 6 + i) : st_get(cb, i)) : ss;
         nsg = tab[ss | (v < 0 ? 256u : 0u)];
     }
     enc_dec(c, s0, !nz);
@@ -482,62 +365,42 @@ __device__ __forceinline__ void enc_symbol_split(Enc &c, uint32_t (&b)[4], uint8
     for (int i = 8; i >= 0; --i)
         if (i < E) enc_dec(c, i < e ? sm[i] : 0u, i < e && ((a >> i) & 1u));
     if (SIGNED && E >= 0) enc_dec(c, nz ? ss : 0u, v < 0);
-    hput(b, 0, n0);
+    st_put(b, 0, n0);
 #pragma unroll
     for (int i = 0; i < 10; ++i)
         if (i <= E) {
-            if (i < 5) hput(b, 1 + i, i <= e ? nu[i] : su[i]);
-            else hput(cb, i - 5, i <= e ? nu[i] : su[i]);
+            if (i < 5) st_put(b, 1 + i, i <= e ? nu[i] : su[i]);
+            else st_put(cb, i - 5, i <= e ? nu[i] : su[i]);
         }
 #pragma unroll
     for (int i = 0; i < 9; ++i)
         if (i < E) {
-            if (i < 4) hput(b, 11 + i, i < e ? nm[i] : sm[i]);
-            else hput(cb, 10 + i - 4, i < e ? nm[i] : sm[i]);
+            if (i < 4) st_put(b, 11 + i, i < e ? nm[i] : sm[i]);
+            else st_put(cb, 10 + i - 4, i < e ? nm[i] : sm[i]);
         }
     if (SIGNED && E >= 0) {
 #pragma unroll
         for (int i = 0; i < 10; ++i) {
             const bool on = nz && es == i;
-            if (i < 5) hput(b, 6 + i, on ? nsg : hget(b, 6 + i));
-            else hput(cb, i, on ? nsg : hget(cb, i));
+            if (i < 5) st_put(b, 6 + i, on ? nsg : st_get(b, 6 + i));
+            else st_put(cb, i, on ? nsg : st_get(cb, i));
         }
     }
-    if (E >= 5) *reinterpret_cast<uint4 *>(cold) = make_uint4(cb[0], cb[1], cb[2], cb[3]);
+    if (E >= 5) hblk_store(cold, cb);
 }
 
-__device__ __forceinline__ void hblk_load(uint32_t (&b)[4], const uint8_t *p) {
-    const uint4 x = *reinterpret_cast<const uint4 *>(p);
-    b[0] = x.x; b[1] = x.y; b[2] = x.z; b[3] = x.w;
-}
-__device__ __forceinline__ void hblk_store(uint8_t *p, const uint32_t (&b)[4]) {
-    *reinterpret_cast<uint4 *>(p) = make_uint4(b[0], b[1], b[2], b[3]);
-}
 __device__ __forceinline__ void hblk_sel(uint32_t (&d)[4], bool c, const uint32_t (&x)[4], const uint32_t (&y)[4]) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) d[i] = c ? x[i] : y[i];
-}
-
-__device__ __forceinline__ void blk_load(uint32_t (&b)[8], const uint8_t *p) {
-    const uint4 x = reinterpret_cast<const uint4 *>(p)[0], y = reinterpret_cast<const uint4 *>(p)[1];
-    b[0] = x.x; b[1] = x.y; b[2] = x.z; b[3] = x.w; b[4] = y.x; b[5] = y.y; b[6] = y.z; b[7] = y.w;
-}
-__device__ __forceinline__ void blk_store(uint8_t *p, const uint32_t (&b)[8]) {
-    reinterpret_cast<uint4 *>(p)[0] = make_uint4(b[0], b[1], b[2], b[3]);
-    reinterpret_cast<uint4 *>(p)[1] = make_uint4(b[4], b[5], b[6], b[7]);
-}
-__device__ __forceinline__ void blk_sel(uint32_t (&d)[8], bool c, const uint32_t (&x)[8], const uint32_t (&y)[8]) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) d[i] = c ? x[i] : y[i];
 }
 
 // 16-bit renorm record of a recorded `low`: low >> 8 (9 bits) | exact << 9
 __device__ __forceinline__ uint32_t rec16(uint32_t low) { return (low >> 8) | ((low & 0xFFu) == 0u ? 0x200u : 0u); }
 
 __global__ __launch_bounds__(64) void ffv1_code_kernel(const Ffv1Args a) {
-    __shared__ uint8_t s_tab[512];  // zero[256], one[256]
+    __shared__ uint8_t s_tab[kTabStates];  // zero[256], one[256]
     __shared__ __align__(16) uint32_t s_ring[64 * kRingStride];
-    for (int i = threadIdx.x; i < 512; i += 64) s_tab[i] = a.tables[i];
+    for (int i = threadIdx.x; i < kTabStates; i += 64) s_tab[i] = a.tables[i];
     __syncthreads();
     const int lane = threadIdx.x;
     if (lane >= a.lpw) return;
@@ -545,13 +408,10 @@ __global__ __launch_bounds__(64) void ffv1_code_kernel(const Ffv1Args a) {
     if (g >= a.nslices) return;
     const SliceGeo q = slice_geo(g, a.w, a.h, a.nh, a.nv, a.hsub, a.vsub);
     const int len = q.len();
-    // context states of the 64-slice group interleaved by slice, hot halves
-    // then cold halves: context k of slice g at [g / 64][half][k][g % 64][16]
-    // -- a 128-B line holds one context's half of 8 slices (a context that is
-    // hot in one slice is hot in its neighbours)
-    uint8_t *const st0 = a.states + (int64_t)(g >> 6) * (64 * a.state_bytes) + (g & 63) * 16;
+    // this slice's context 0 (state layout: ffv1_dev.hpp); a 64-slice group
+    // holds its hot halves, then its cold halves
+    uint8_t *const st0 = state_at(a.states, g, 0, a.state_bytes);
     uint8_t *const co0 = st0 + 64 * a.state_bytes / 2;
-    constexpr int kCtxStride = 64 * 16;
     // tokens of slice g: group g / 64 of the modelling layout, lane g % 64
     const uint32_t *tp = a.tok + (int64_t)(g >> 6) * a.tok_len * 64 + (g & 63);
     Enc c;
@@ -671,7 +531,7 @@ __global__ __launch_bounds__(64) void ffv1_resolve_kernel(const Ffv1Args a) {
     // bytes, so a whole output word updates the CRC with 4 independent lookups
     // (one LDS latency on the chain per 4 bytes instead of per byte)
     __shared__ uint32_t s_crc[4][256];
-    for (int i = threadIdx.x; i < 256; i += 64) s_crc[0][i] = reinterpret_cast<const uint32_t *>(a.tables + 512)[i];
+    for (int i = threadIdx.x; i < 256; i += 64) s_crc[0][i] = reinterpret_cast<const uint32_t *>(a.tables + kTabCrc)[i];
     __syncthreads();
     for (int k = 1; k < 4; ++k) {
         for (int i = threadIdx.x; i < 256; i += 64) {
@@ -800,7 +660,7 @@ struct pp_ffv1_enc {
     int64_t pk_cap = 0, pk_len = 0;
     int launches = 0;          // launches of the last encode (> 1: a batch was split)
     Ffv1Quant quant;           // the record's 3-input quantiser
-    int64_t state_bytes() const { return (int64_t)2 * quant.contexts() * kCtxSize; }
+    int64_t state_bytes() const { return (int64_t)2 * quant.contexts() * kFfv1CtxBytes; }
     std::vector<uint8_t> extradata;
 };
 
@@ -832,7 +692,7 @@ extern "C" int pp_ffv1_encoder_create(pp_ctx *ctx, int fmt, int w, int h, int sl
     auto covers = [](int n, int ns, int sub) {
         int end = 0;
         for (int i = 0; i < ns; ++i) {
-            const int a = (int)((int64_t)i * n / ns), b = (int)((int64_t)(i + 1) * n / ns);
+            const int a = slice_edge(i, n, ns), b = slice_edge(i + 1, n, ns);
             if ((a >> sub) > end) return false;
             end = std::max(end, (a >> sub) + (((b - a) + (1 << sub) - 1) >> sub));
         }
@@ -893,10 +753,10 @@ extern "C" int pp_ffv1_encoder_create(pp_ctx *ctx, int fmt, int w, int h, int sl
     PP_HIP(hipMalloc(&E->tok, sizeof(uint32_t) * (size_t)(ns64 * len_max)));
     PP_HIP(hipMalloc(&E->raw, sizeof(uint32_t) * (size_t)E->budget));
     PP_HIP(hipMalloc(&E->nraw, sizeof(int32_t) * ns));
-    PP_HIP(hipMalloc(&E->tables, 512 + 1024));
-    uint8_t tab[512 + 1024];
-    rac_states(tab, tab + 256);
-    crc_table(reinterpret_cast<uint32_t *>(tab + 512));
+    PP_HIP(hipMalloc(&E->tables, kTabBytes));
+    uint8_t tab[kTabBytes];
+    rac_states(tab + kTabZero, tab + kTabOne);
+    crc_table(reinterpret_cast<uint32_t *>(tab + kTabCrc));
     PP_HIP(hipMemcpy(E->tables, tab, sizeof(tab), hipMemcpyHostToDevice));
     *out = E.release();
     return PP_OK;
@@ -922,7 +782,7 @@ extern "C" int pp_ffv1_encoder_memory(const pp_ffv1_enc *E, int64_t *bytes) {
     if (!E || !bytes) PP_FAIL(PP_ERR_INVALID, "null argument");
     const int64_t ns = (int64_t)E->nh * E->nv * E->max_frames, ns64 = (ns + 63) / 64 * 64;
     *bytes = E->ctx ? E->state_bytes() * ns64 + (8 + 8 + 4 + 4) * ns + 4 * ns64 * E->tok_len + 4 * E->budget +
-                          1536 + E->pk_cap
+                          kTabBytes + E->pk_cap
                     : 0;
     return PP_OK;
 }
@@ -1028,7 +888,7 @@ extern "C" int64_t pp_ffv1_encode_packets(pp_ffv1_enc *E, const pp_frames *src, 
         PP_HIP(hipMemcpyAsync(E->off, off.data(), sizeof(int64_t) * ns, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(ffv1_pack_kernel, dim3(ns), dim3(256), 0, st, reinterpret_cast<const uint8_t *>(E->raw),
                            rcap * 4, E->sizes, E->crcs, E->off, E->pk,
-                           reinterpret_cast<const uint32_t *>(E->tables + 512));
+                           reinterpret_cast<const uint32_t *>(E->tables + kTabCrc));
         PP_HIP(hipGetLastError());
         // the next launch reuses the records, the sizes and the offsets
         PP_HIP(hipStreamSynchronize(st));

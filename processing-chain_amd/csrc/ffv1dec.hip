@@ -26,6 +26,7 @@
 
 #include "common.hpp"
 #include "device.hpp"
+#include "ffv1_dev.hpp"
 #include "ffv1host.hpp"
 
 namespace pp {
@@ -55,7 +56,7 @@ struct Ffv1DecArgs {
     uint8_t *states;             // hot halves [nchains / 64][2 * max_ctx][64][16]
     uint8_t *cold;               // cold halves, same layout
     int *status;                 // [nframes * per], zeroed by the host
-    const uint8_t *tables;       // zero[256], one[256] (the record's), crc table, x^(8 * 2^j)
+    const uint8_t *tables;       // the table blob (ffv1_dev.hpp), zero / one the record's
     const int16_t *quant;        // [ntables][5][256] (scaled)
     const uint4 *init;           // [contexts][hot 16 | cold 16] initial states, split as the state halves
     int qthr[5];                 // PIX: the first quantiser's thresholds (Ffv1Quant), unused ones 1024
@@ -111,16 +112,13 @@ __device__ __forceinline__ uint32_t dec_rac(Dec &d, uint32_t s, const uint8_t *t
     return bit;
 }
 
-__device__ __forceinline__ uint32_t dsget(const uint32_t (&b)[8], int k) { return (b[k >> 2] >> ((k & 3) * 8)) & 0xFFu; }
-__device__ __forceinline__ void dsput(uint32_t (&b)[8], int k, uint32_t v) {
-    b[k >> 2] = (b[k >> 2] & ~(0xFFu << ((k & 3) * 8))) | (v << ((k & 3) * 8));
-}
-__device__ __forceinline__ uint32_t dsget_dyn(const uint32_t (&b)[8], int k) {  // k in 8..23
+// state byte k of an 8-dword block at a runtime index k in 8..23 (the sign state 11 + e)
+__device__ __forceinline__ uint32_t dec_get_dyn(const uint32_t (&b)[8], int k) {
     const int w = k >> 2;
     const uint32_t x = w == 2 ? b[2] : w == 3 ? b[3] : w == 4 ? b[4] : b[5];
     return (x >> ((k & 3) * 8)) & 0xFFu;
 }
-__device__ __forceinline__ void dsput_dyn(uint32_t (&b)[8], int k, uint32_t v) {
+__device__ __forceinline__ void dec_put_dyn(uint32_t (&b)[8], int k, uint32_t v) {
     const int w = k >> 2;
     const uint32_t sh = (k & 3) * 8, m = ~(0xFFu << sh), nv = v << sh;
     b[2] = w == 2 ? (b[2] & m) | nv : b[2];
@@ -135,7 +133,7 @@ __device__ __forceinline__ void dsput_dyn(uint32_t (&b)[8], int k, uint32_t v) {
 template <bool SIGNED>
 __device__ __forceinline__ int dec_symbol(Dec &d, uint32_t (&b)[8], const uint8_t *tab, bool &bad) {
     uint32_t n0;
-    const uint32_t z = dec_rac(d, dsget(b, 0), tab, n0);
+    const uint32_t z = dec_rac(d, st_get(b, 0), tab, n0);
     uint32_t nu[10], nm[9], nsg = 0;
     int e = 0, a = 1;
     uint32_t neg = 0;
@@ -144,71 +142,61 @@ __device__ __forceinline__ int dec_symbol(Dec &d, uint32_t (&b)[8], const uint8_
 #pragma unroll
         for (int i = 0; i < 10; ++i)
             if (go) {
-                if (dec_rac(d, dsget(b, 1 + i), tab, nu[i])) e = i + 1;
+                if (dec_rac(d, st_get(b, 1 + i), tab, nu[i])) e = i + 1;
                 else go = false;
             }
         if (go) bad = true;
 #pragma unroll
         for (int i = 8; i >= 0; --i)
-            if (i < e) a = 2 * a + (int)dec_rac(d, dsget(b, 22 + i), tab, nm[i]);
-        if constexpr (SIGNED) neg = dec_rac(d, dsget_dyn(b, 11 + min(e, 9)), tab, nsg);
+            if (i < e) a = 2 * a + (int)dec_rac(d, st_get(b, 22 + i), tab, nm[i]);
+        if constexpr (SIGNED) neg = dec_rac(d, dec_get_dyn(b, 11 + min(e, 9)), tab, nsg);
     }
-    dsput(b, 0, n0);
+    st_put(b, 0, n0);
     if (!z) {
 #pragma unroll
         for (int i = 0; i < 10; ++i)
-            if (i <= e) dsput(b, 1 + i, nu[i]);
+            if (i <= e) st_put(b, 1 + i, nu[i]);
 #pragma unroll
         for (int i = 0; i < 9; ++i)
-            if (i < e) dsput(b, 22 + i, nm[i]);
-        if constexpr (SIGNED) dsput_dyn(b, 11 + min(e, 9), nsg);
+            if (i < e) st_put(b, 22 + i, nm[i]);
+        if constexpr (SIGNED) dec_put_dyn(b, 11 + min(e, 9), nsg);
     }
     return z ? 0 : (neg ? -a : a);
 }
 
-// A context's 32 state bytes split in two 16-byte halves.  HOT (the block
-// loaded on every context switch): [0] zero flag, [1..5] exponent
-// bits 0..4, [6..10] sign for e = 0..4, [11..14] mantissa bits 0..3 -- every
-// state a residual below 32 in magnitude touches.  COLD (its own array):
-// [0..4] exponent bits 5..9, [5..9] sign for e = 5..9, [10..14] mantissa bits
-// 4..8, loaded only once a symbol's exponent reaches 5.
-__device__ __forceinline__ uint32_t bget(const uint32_t (&b)[4], int k) { return (b[k >> 2] >> ((k & 3) * 8)) & 0xFFu; }
-__device__ __forceinline__ void bput(uint32_t (&b)[4], int k, uint32_t v) {
-    b[k >> 2] = (b[k >> 2] & ~(0xFFu << ((k & 3) * 8))) | (v << ((k & 3) * 8));
-}
-
 // get_symbol (ffv1dec.c) for samples of <= 10 bits: exponent e <= 9, so every
 // state index is used at most once per symbol; e >= 10 (not a <= 10-bit
-// stream) sets `bad`.  Decisions read the block as loaded and write the next
+// stream) sets `bad`, on the split block (HOT in `h`, COLD at `cold`:
+// ffv1_dev.hpp).  Decisions read the block as loaded and write the next
 // states into a copy, so no decision waits on the previous one's state-table
 // lookup (neighbouring state bytes share a dword).
 template <bool SIGNED>
 __device__ __forceinline__ int dec_symbol_split(Dec &d, uint32_t (&h)[4], uint8_t *cold, const uint8_t *tab, bool &bad) {
     const uint32_t h0[4] = {h[0], h[1], h[2], h[3]};
     uint32_t ns;
-    const uint32_t z = dec_rac(d, bget(h0, 0), tab, ns);
-    bput(h, 0, ns);
+    const uint32_t z = dec_rac(d, st_get(h0, 0), tab, ns);
+    st_put(h, 0, ns);
     if (z) return 0;
     int e = 0, a = 1;
     bool go = true;
 #pragma unroll
     for (int i = 0; i < 5; ++i)
         if (go) {
-            const uint32_t bit = dec_rac(d, bget(h0, 1 + i), tab, ns);
-            bput(h, 1 + i, ns);
+            const uint32_t bit = dec_rac(d, st_get(h0, 1 + i), tab, ns);
+            st_put(h, 1 + i, ns);
             if (bit) e = i + 1;
             else go = false;
         }
     uint32_t neg;
     if (go) {  // e >= 5: the cold half
-        const uint4 x = *reinterpret_cast<const uint4 *>(cold);
-        const uint32_t c0[4] = {x.x, x.y, x.z, x.w};
-        uint32_t c[4] = {x.x, x.y, x.z, x.w};
+        uint32_t c[4];
+        hblk_load(c, cold);
+        const uint32_t c0[4] = {c[0], c[1], c[2], c[3]};
 #pragma unroll
         for (int i = 5; i < 10; ++i)
             if (go) {
-                const uint32_t bit = dec_rac(d, bget(c0, i - 5), tab, ns);
-                bput(c, i - 5, ns);
+                const uint32_t bit = dec_rac(d, st_get(c0, i - 5), tab, ns);
+                st_put(c, i - 5, ns);
                 if (bit) e = i + 1;
                 else go = false;
             }
@@ -216,42 +204,42 @@ __device__ __forceinline__ int dec_symbol_split(Dec &d, uint32_t (&h)[4], uint8_
 #pragma unroll
         for (int i = 8; i >= 4; --i)
             if (i < e) {
-                a = 2 * a + (int)dec_rac(d, bget(c0, 10 + i - 4), tab, ns);
-                bput(c, 10 + i - 4, ns);
+                a = 2 * a + (int)dec_rac(d, st_get(c0, 10 + i - 4), tab, ns);
+                st_put(c, 10 + i - 4, ns);
             }
 #pragma unroll
         for (int i = 3; i >= 0; --i) {
-            a = 2 * a + (int)dec_rac(d, bget(h0, 11 + i), tab, ns);
-            bput(h, 11 + i, ns);
+            a = 2 * a + (int)dec_rac(d, st_get(h0, 11 + i), tab, ns);
+            st_put(h, 11 + i, ns);
         }
         neg = 0;
         if constexpr (SIGNED) {
             const int k = min(e, 9);  // sign state 5 + (k - 5) of the cold half
-            const uint32_t sv = k == 5 ? bget(c0, 5) : k == 6 ? bget(c0, 6) : k == 7 ? bget(c0, 7) : k == 8 ? bget(c0, 8) : bget(c0, 9);
+            const uint32_t sv = k == 5 ? st_get(c0, 5) : k == 6 ? st_get(c0, 6) : k == 7 ? st_get(c0, 7) : k == 8 ? st_get(c0, 8) : st_get(c0, 9);
             neg = dec_rac(d, sv, tab, ns);
-            if (k == 5) bput(c, 5, ns);
-            else if (k == 6) bput(c, 6, ns);
-            else if (k == 7) bput(c, 7, ns);
-            else if (k == 8) bput(c, 8, ns);
-            else bput(c, 9, ns);
+            if (k == 5) st_put(c, 5, ns);
+            else if (k == 6) st_put(c, 6, ns);
+            else if (k == 7) st_put(c, 7, ns);
+            else if (k == 8) st_put(c, 8, ns);
+            else st_put(c, 9, ns);
         }
-        *reinterpret_cast<uint4 *>(cold) = make_uint4(c[0], c[1], c[2], c[3]);
+        hblk_store(cold, c);
     } else {
 #pragma unroll
         for (int i = 3; i >= 0; --i)
             if (i < e) {
-                a = 2 * a + (int)dec_rac(d, bget(h0, 11 + i), tab, ns);
-                bput(h, 11 + i, ns);
+                a = 2 * a + (int)dec_rac(d, st_get(h0, 11 + i), tab, ns);
+                st_put(h, 11 + i, ns);
             }
         neg = 0;
         if constexpr (SIGNED) {  // sign state 6 + e, e in 0..4
-            const uint32_t sv = e == 0 ? bget(h0, 6) : e == 1 ? bget(h0, 7) : e == 2 ? bget(h0, 8) : e == 3 ? bget(h0, 9) : bget(h0, 10);
+            const uint32_t sv = e == 0 ? st_get(h0, 6) : e == 1 ? st_get(h0, 7) : e == 2 ? st_get(h0, 8) : e == 3 ? st_get(h0, 9) : st_get(h0, 10);
             neg = dec_rac(d, sv, tab, ns);
-            if (e == 0) bput(h, 6, ns);
-            else if (e == 1) bput(h, 7, ns);
-            else if (e == 2) bput(h, 8, ns);
-            else if (e == 3) bput(h, 9, ns);
-            else bput(h, 10, ns);
+            if (e == 0) st_put(h, 6, ns);
+            else if (e == 1) st_put(h, 7, ns);
+            else if (e == 2) st_put(h, 8, ns);
+            else if (e == 3) st_put(h, 9, ns);
+            else st_put(h, 10, ns);
         }
     }
     return neg ? -a : a;
@@ -268,29 +256,8 @@ __device__ __forceinline__ uint32_t gf2_mulmod(uint32_t a, uint32_t b) {
     return r;
 }
 
-__device__ __forceinline__ void dblk_load(uint32_t (&b)[8], const uint8_t *p) {
-    const uint4 x = reinterpret_cast<const uint4 *>(p)[0], y = reinterpret_cast<const uint4 *>(p)[1];
-    b[0] = x.x; b[1] = x.y; b[2] = x.z; b[3] = x.w; b[4] = y.x; b[5] = y.y; b[6] = y.z; b[7] = y.w;
-}
-__device__ __forceinline__ void dblk_store(uint8_t *p, const uint32_t (&b)[8]) {
-    reinterpret_cast<uint4 *>(p)[0] = make_uint4(b[0], b[1], b[2], b[3]);
-    reinterpret_cast<uint4 *>(p)[1] = make_uint4(b[4], b[5], b[6], b[7]);
-}
-
-
-__device__ __forceinline__ int dmedian3(int a, int b, int c) { return max(min(a, b), min(max(a, b), c)); }
-
-// A pixpath-form first quantiser (ffv1host.cpp ffv1_quant: the number of
-// thresholds <= |d|, odd-mirrored, scale 1) as ALU code: the only lookup that
-// depends on the sample just decoded leaves LDS
-__device__ __forceinline__ int dquant0(int d, const int (&thr)[5]) {  // d already & 0xFF
-    const int m = d < 128 ? d : (d == 128 ? 127 : 256 - d);
-    const int q = (m >= thr[0]) + (m >= thr[1]) + (m >= thr[2]) + (m >= thr[3]) + (m >= thr[4]);
-    return d < 128 ? q : -q;
-}
-
 // Copy chain states (both halves, every context) between two slot arrays of
-// the [slot / 64][nctx][64][16] layout: the GOP carried into the next decode.
+// the state layout (ffv1_dev.hpp): the GOP carried into the next decode.
 __global__ __launch_bounds__(256) void ffv1_state_copy_kernel(const uint8_t *src, int64_t src_half, int src_slot0,
                                                               uint8_t *dst, int64_t dst_half, int dst_slot0, int nslots,
                                                               int nctx) {
@@ -300,12 +267,13 @@ __global__ __launch_bounds__(256) void ffv1_state_copy_kernel(const uint8_t *src
     const int half = (int)(i / per_half);
     const int64_t r = i - half * per_half;
     const int slot = (int)(r % nslots), k = (int)(r / nslots);
-    auto at = [&](int sl) { return (int64_t)(sl >> 6) * (64 * (int64_t)nctx * 16) + (int64_t)k * 1024 + (sl & 63) * 16; };
+    auto at = [&](int sl) { return (int64_t)(sl >> 6) * (64 * (int64_t)nctx * 16) + (int64_t)k * kCtxStride + (sl & 63) * 16; };
     const uint4 v = *reinterpret_cast<const uint4 *>(src + half * src_half + at(src_slot0 + slot));
     *reinterpret_cast<uint4 *>(dst + half * dst_half + at(dst_slot0 + slot)) = v;
 }
 
 // PIX: the record is pixpath's own 3-input set (first quantiser as ALU code,
+// dquant: the only lookup that depends on the sample just decoded leaves LDS;
 // one LDS line row per lane); else the general 5-input context
 // (ffv1_template.c get_context) over two line rows -- the row above and the
 // row two above, which the current row overwrites in place (decode_plane's
@@ -314,19 +282,19 @@ __global__ __launch_bounds__(256) void ffv1_state_copy_kernel(const uint8_t *src
 // 3-input context.
 template <int BYTES, bool PIX>
 __global__ __launch_bounds__(64) void ffv1_decode_kernel(const Ffv1DecArgs a) {
-    __shared__ uint8_t s_tab[512];  // zero[256], one[256]
+    __shared__ uint8_t s_tab[kTabStates];  // zero[256], one[256]
     __shared__ uint32_t s_crc[256];
     __shared__ uint32_t s_xp[32];   // x^(8 * 2^j) mod P
     extern __shared__ __align__(16) int16_t s_dyn[];  // [ntables][5][256] quantisers, then [lpw][rows][row_cap] lines
     const int lane = threadIdx.x;
     for (int i = lane; i < 256; i += blockDim.x) {
-        s_tab[i] = a.tables[i];
-        s_tab[256 + i] = a.tables[256 + i];
-        s_crc[i] = reinterpret_cast<const uint32_t *>(a.tables + 512)[i];
+        s_tab[kTabZero + i] = a.tables[kTabZero + i];
+        s_tab[kTabOne + i] = a.tables[kTabOne + i];
+        s_crc[i] = reinterpret_cast<const uint32_t *>(a.tables + kTabCrc)[i];
     }
     const int nq = a.ntables * 5 * 256;
     for (int i = lane; i < nq; i += blockDim.x) s_dyn[i] = a.quant[i];
-    if (lane < 32) s_xp[lane] = reinterpret_cast<const uint32_t *>(a.tables + 1536)[lane];
+    if (lane < 32) s_xp[lane] = reinterpret_cast<const uint32_t *>(a.tables + kTabXp)[lane];
     __syncthreads();
     const int c = blockIdx.x * a.lpw + lane;  // this lane's chain
     if (a.ec && !(PP_ABLATE(a.debug) & 2)) {
@@ -367,13 +335,11 @@ __global__ __launch_bounds__(64) void ffv1_decode_kernel(const Ffv1DecArgs a) {
     const int kg = c / a.per, s = c - kg * a.per;
     const int f0 = a.gop[3 * kg], nf = a.gop[3 * kg + 1], key_start = a.gop[3 * kg + 2] & 1;
     uint16_t *const lines = reinterpret_cast<uint16_t *>(s_dyn + nq) + lane * a.row_cap * (PIX ? 1 : 2);
-    // context states of 64 neighbouring chains interleaved by chain (as the
-    // encoder's): context k of chain c at [c / 64][k][c % 64], so a context
-    // that is hot in neighbouring slices -- the same picture content -- shares
-    // their 128-B lines in L2 instead of one line per slice
+    // this chain's context 0 in the hot and the cold array: state_at
+    // (ffv1_dev.hpp) written out, as in the copy kernel above and at the two
+    // block stores below -- through the helpers this kernel's code changes
     uint8_t *const st0 = a.states + (int64_t)(c >> 6) * (64 * a.state_bytes) + (c & 63) * 16;
     uint8_t *const co0 = a.cold + (int64_t)(c >> 6) * (64 * a.state_bytes) + (c & 63) * 16;
-    constexpr int kCtxStride = 64 * 16;
     const int mask = (1 << a.bits) - 1;
     for (int j = 0; j < nf; ++j) {
         const int64_t g = (int64_t)(f0 + j) * a.per + s;  // (frame, slice) of this step
@@ -413,8 +379,8 @@ __global__ __launch_bounds__(64) void ffv1_decode_kernel(const Ffv1DecArgs a) {
             a.status[g] = 2;
             return;
         }
-        const int x0 = (int)((int64_t)sx * a.w / a.nh), x1 = (int)((int64_t)(sx + sw) * a.w / a.nh);
-        const int y0 = (int)((int64_t)sy * a.h / a.nv), y1 = (int)((int64_t)(sy + sh) * a.h / a.nv);
+        const int x0 = slice_edge(sx, a.w, a.nh), x1 = slice_edge(sx + sw, a.w, a.nh);
+        const int y0 = slice_edge(sy, a.h, a.nv), y1 = slice_edge(sy + sh, a.h, a.nv);
         if (x1 - x0 > a.row_cap) {  // wider than this grid's slices
             a.status[g] = 2;
             return;
@@ -434,10 +400,7 @@ __global__ __launch_bounds__(64) void ffv1_decode_kernel(const Ffv1DecArgs a) {
         // block back, so it must start as the stored one)
         int cur_key = 0;
         uint32_t blk[4];
-        {
-            const uint4 b0 = *reinterpret_cast<const uint4 *>(st0);
-            blk[0] = b0.x; blk[1] = b0.y; blk[2] = b0.z; blk[3] = b0.w;
-        }
+        hblk_load(blk, st0);
         for (int p = 0; p < 3; p++) {
             const int pw = p ? ((x1 - x0) + (1 << a.hsub) - 1) >> a.hsub : x1 - x0;
             const int ph = p ? ((y1 - y0) + (1 << a.vsub) - 1) >> a.vsub : y1 - y0;
@@ -480,7 +443,7 @@ __global__ __launch_bounds__(64) void ffv1_decode_kernel(const Ffv1DecArgs a) {
                     if constexpr (!PIX) nTT = (y > 1 && x + 1 < pw) ? two[x + 1] : 0;
                     int ctx;
                     if constexpr (PIX)
-                        ctx = dquant0((L - TL) & 0xFF, a.qthr) + q[256 + ((TL - T) & 0xFF)] + q[512 + ((T - TR) & 0xFF)];
+                        ctx = dquant((L - TL) & 0xFF, a.qthr) + q[256 + ((TL - T) & 0xFF)] + q[512 + ((T - TR) & 0xFF)];
                     else
                         ctx = q[(L - TL) & 0xFF] + q[256 + ((TL - T) & 0xFF)] + q[512 + ((T - TR) & 0xFF)] +
                               q[768 + ((LL - L) & 0xFF)] + q[1024 + ((TT - T) & 0xFF)];
@@ -507,7 +470,7 @@ __global__ __launch_bounds__(64) void ffv1_decode_kernel(const Ffv1DecArgs a) {
                     }
                     int diff = dec_symbol_split<true>(d, blk, co0 + cur_key * kCtxStride, s_tab, bad);
                     if (neg) diff = -diff;
-                    const int v = (dmedian3(L, L + T - TL, T) + diff) & mask;
+                    const int v = (median3(L, L + T - TL, T) + diff) & mask;
                     pv = v;  // stored during the next sample, after its block load
                     two[x] = (uint16_t)v;  // PIX: `two` is the one line (x is no longer T or TR)
                     TL = T;
@@ -546,12 +509,12 @@ struct pp_ffv1_dec {
     bool pix = false;  // pixpath's own 3-input set (ALU first quantiser, one line row)
     Ffv1Quant pq;      // its thresholds
     uint8_t *pkt = nullptr, *states = nullptr, *tables = nullptr, *carry = nullptr;
-    int64_t pkt_cap = 0, *soff = nullptr, *slen = nullptr;
+    int64_t pkt_cap = 0;
+    int64_t *slices = nullptr;  // one array per decode: soff[ns] | slen[ns] | status[ns] (int)
     int *gop = nullptr;
     int row_cap = 0;  // widest slice row, rounded to 8 samples
     int lpw = 16;     // chains per workgroup: 16, fewer when their line buffers would not fit the LDS
     size_t lds = 0;   // dynamic LDS per workgroup at lpw: quantisers + line rows
-    int *status = nullptr;
     int16_t *dquant = nullptr;
     uint4 *dinit = nullptr;
     int init_off[kFfv1MaxTables];
@@ -559,31 +522,13 @@ struct pp_ffv1_dec {
     // record with thousands of contexts no longer reserves per * max_frames
     // chain slots up front -- a GOP-12 stream needs a twelfth of them)
     int64_t slots = 0;        // chain state slots allocated (64-aligned)
-    int64_t ns_cap = 0;       // slice entries (soff / slen / status)
+    int64_t ns_cap = 0;       // slice entries (`slices`)
     int64_t gop_cap = 0;      // GOP entries
     bool carry_valid = false; // `carry` holds the last GOP's states of the previous decode
     std::vector<uint8_t> extra;  // the configuration record (a group decode needs equal ones)
 };
 
 namespace {
-
-// a context's 32 FFmpeg state bytes -> the HOT | COLD halves of the decoder
-// (dec_symbol_split): HOT [0] zero, [1..5] exponent 0..4, [6..10] sign e = 0..4,
-// [11..14] mantissa 0..3; COLD [0..4] exponent 5..9, [5..9] sign e = 5..9,
-// [10..14] mantissa 4..8 (states 21 and 31 serve > 10-bit samples only)
-void split_states(const uint8_t *st, uint8_t hot[16], uint8_t cold[16]) {
-    std::memset(hot, 128, 16);
-    std::memset(cold, 128, 16);
-    hot[0] = st[0];
-    for (int i = 0; i < 5; ++i) {
-        hot[1 + i] = st[1 + i];
-        hot[6 + i] = st[11 + i];
-        cold[i] = st[6 + i];
-        cold[5 + i] = st[16 + i];
-        cold[10 + i] = st[26 + i];
-    }
-    for (int i = 0; i < 4; ++i) hot[11 + i] = st[22 + i];
-}
 
 // A record of pixpath's form: one set of 3 inputs whose quantisers are one
 // threshold quantiser (Ffv1Quant, up to 5 thresholds) at scales 1, L, L^2 --
@@ -625,7 +570,7 @@ extern "C" int pp_ffv1_decoder_create(pp_ctx *ctx, const uint8_t *extra, int ext
     D->pix = pixpath_tables(R, &D->pq);
     int wmax = 0;
     for (int i = 0; i < R.nh; ++i)
-        wmax = std::max(wmax, (int)((int64_t)(i + 1) * w / R.nh - (int64_t)i * w / R.nh));
+        wmax = std::max(wmax, slice_edge(i + 1, w, R.nh) - slice_edge(i, w, R.nh));
     D->row_cap = (wmax + 7) / 8 * 8;
     const size_t qbytes = (size_t)R.ntables * 5 * 256 * 2, rows = D->pix ? 1 : 2;
     const size_t per_lane = (size_t)D->row_cap * 2 * rows;
@@ -648,14 +593,14 @@ extern "C" int pp_ffv1_decoder_create(pp_ctx *ctx, const uint8_t *extra, int ext
     const int64_t chalf = 2 * (int64_t)R.max_ctx * 16 * ((per + 63) / 64 * 64);
     PP_HIP(hipSetDevice(ctx->device));
     PP_HIP(hipMalloc(&D->carry, 2 * chalf));  // the decode workspace itself is allocated by the first decode
-    PP_HIP(hipMalloc(&D->tables, 512 + 1024 + 128));
+    PP_HIP(hipMalloc(&D->tables, kTabBytesXp));
     PP_HIP(hipMalloc(&D->dquant, qbytes));
-    uint8_t tab[512 + 1024 + 128];
-    std::memcpy(tab, R.zero_state, 256);
-    std::memcpy(tab + 256, R.one_state, 256);
-    crc_table(reinterpret_cast<uint32_t *>(tab + 512));
+    uint8_t tab[kTabBytesXp];
+    std::memcpy(tab + kTabZero, R.zero_state, 256);
+    std::memcpy(tab + kTabOne, R.one_state, 256);
+    crc_table(reinterpret_cast<uint32_t *>(tab + kTabCrc));
     {  // x^(8 * 2^j) mod P by squaring, from x^8
-        uint32_t *xp = reinterpret_cast<uint32_t *>(tab + 1536);
+        uint32_t *xp = reinterpret_cast<uint32_t *>(tab + kTabXp);
         auto mulmod = [](uint32_t x, uint32_t y) {
             uint32_t r = 0;
             for (int i = 31; i >= 0; --i) {
@@ -674,7 +619,7 @@ extern "C" int pp_ffv1_decoder_create(pp_ctx *ctx, const uint8_t *extra, int ext
         for (int t = 0; t < R.ntables; ++t)
             for (int k = 0; D->init_off[t] >= 0 && k < R.ctx_count[t]; ++k) {
                 uint8_t *o = split.data() + (size_t)(D->init_off[t] + k) * 32;
-                split_states(R.init[t].data() + (size_t)k * 32, o, o + 16);
+                split_states(R.init[t].data() + (size_t)k * 32, o, o + 16);  // HOT | COLD (ffv1_dev.hpp)
             }
         PP_HIP(hipMalloc(&D->dinit, split.size()));
         PP_HIP(hipMemcpy(D->dinit, split.data(), split.size(), hipMemcpyHostToDevice));
@@ -685,8 +630,7 @@ extern "C" int pp_ffv1_decoder_create(pp_ctx *ctx, const uint8_t *extra, int ext
 
 extern "C" int pp_ffv1_decoder_destroy(pp_ffv1_dec *D) {
     if (!D) return PP_OK;
-    for (void *p : {(void *)D->pkt, (void *)D->states, (void *)D->carry, (void *)D->soff, (void *)D->slen,
-                    (void *)D->status, (void *)D->gop, (void *)D->tables, (void *)D->dquant, (void *)D->dinit})
+    for (void *p : {(void *)D->pkt, (void *)D->states, (void *)D->carry, (void *)D->slices, (void *)D->gop, (void *)D->tables, (void *)D->dquant, (void *)D->dinit})
         if (p) (void)hipFree(p);
     delete D;
     return PP_OK;
@@ -734,15 +678,15 @@ extern "C" int pp_ffv1_decoder_reset(pp_ffv1_dec *D) {
 
 namespace {
 
-// grow a device array to at least `need` elements (the decode is synchronous,
-// so no earlier launch still uses the old one)
+// grow a device array to `need` of the units its capacity counts, `bytes` in
+// all (the decode is synchronous, so no earlier launch still uses the old one)
 template <typename T>
-hipError_t grow(T **p, int64_t *cap, int64_t need) {
+hipError_t grow(T **p, int64_t *cap, int64_t need, size_t bytes) {
     if (need <= *cap) return hipSuccess;
     if (*p) (void)hipFree(*p);
     *p = nullptr;
     *cap = 0;
-    if (hipError_t e = hipMalloc(p, sizeof(T) * need)) return e;
+    if (hipError_t e = hipMalloc(p, bytes)) return e;
     *cap = need;
     return hipSuccess;
 }
@@ -774,77 +718,40 @@ static int decode_group(pp_ffv1_dec *const *decs, int n, const uint8_t *const *p
     hipStream_t st = static_cast<hipStream_t>(stream);
     PP_HIP(hipSetDevice(D->ctx->device));
     const int per = R.nh * R.nv;
-    int64_t ftot = 0;
-    for (int k = 0; k < n; ++k) ftot += nframes[k];
-    if (ftot == 0) return PP_OK;
-    const int64_t ns = per * ftot;
-    std::vector<int64_t> soff(ns), slen(ns), bytes(n);
-    std::vector<int> gop, first_gop(n), ngop(n);
+    // plan: slice tables, GOPs and packet windows (ffv1host.cpp)
     std::vector<char> carry_in(n);
+    for (int k = 0; k < n; ++k) carry_in[k] = decs[k]->carry_valid;
+    Ffv1GroupPlan P;
     std::string err;
-    int64_t base = 0, f0 = 0;
-    for (int k = 0; k < n; ++k) {  // slice tables and GOPs, stream by stream
-        pp_ffv1_dec *E = decs[k];
-        carry_in[k] = E->carry_valid;
-        first_gop[k] = (int)gop.size() / 3;
-        const int nf = nframes[k];
-        if (nf == 0) continue;
-        E->carry_valid = false;  // until this decode has succeeded
-        int64_t sb = 0;
-        if (int rc = ffv1_slice_table(packets[k], frame_sizes[k], nf, per, R.ec, soff.data() + f0 * per,
-                                      slen.data() + f0 * per, &sb, &err))
-            PP_FAIL(rc, "stream %d: %s", k, err.c_str());
-        for (int64_t i = f0 * per; i < (f0 + nf) * per; ++i) soff[i] += base;
-        for (int f = 0; f < nf; ++f) {  // a keyframe starts a GOP; frame 0 without one continues the carried one
-            const int64_t s0 = (f0 + f) * per;
-            const int key = ffv1_keyframe_bit(packets[k] + soff[s0] - base, slen[s0]);
-            if (f == 0 || key) {
-                if (f == 0 && !key && !carry_in[k])
-                    PP_FAIL(PP_ERR_INVALID, "stream %d: frame 0 is not a keyframe and no earlier frame of its GOP "
-                                            "was decoded", k);
-                gop.insert(gop.end(), {(int)(f0 + f), 0, key});
-            }
-            gop[gop.size() - 2]++;
-        }
-        ngop[k] = (int)gop.size() / 3 - first_gop[k];
-        bytes[k] = sb;
-        base += (sb + 63) & ~int64_t(63);
-        f0 += nf;
+    int failed = 0;
+    if (int rc = ffv1_plan_group(n, packets, frame_sizes, nframes, carry_in.data(), per, R.ec, &P, &failed, &err)) {
+        // ADVICE r6 (carry_valid): the streams before the failed one lose their carried GOP as well,
+        // though nothing of theirs was touched; dropping this loop is the fix (with its retry test)
+        for (int k = 0; k <= failed; ++k)
+            if (nframes[k]) decs[k]->carry_valid = false;
+        PP_FAIL(rc, "stream %d: %s", failed, err.c_str());
     }
+    if (P.ftot == 0) return PP_OK;
+    for (int k = 0; k < n; ++k)
+        if (nframes[k]) decs[k]->carry_valid = false;  // until this decode has succeeded
+    const std::vector<int> &gop = P.gop, &first_gop = P.first_gop, &ngop = P.ngop;
+    const int64_t ns = per * P.ftot;
     const int ngops = (int)gop.size() / 3, nchains = ngops * per;
-    if (base > D->pkt_cap) {
-        if (D->pkt) PP_HIP(hipFree(D->pkt));
-        D->pkt = nullptr;
-        D->pkt_cap = 0;
-        PP_HIP(hipMalloc(&D->pkt, base + 64));  // the bytestream window reads up to 8 B past a slice
-        D->pkt_cap = base;
-    }
+    // grow and upload
     const int64_t sb = 2 * (int64_t)R.max_ctx * 16;  // one half, per chain
     const int64_t need_slots = ((int64_t)nchains + 63) / 64 * 64;
-    if (need_slots > D->slots) {
-        if (D->states) PP_HIP(hipFree(D->states));
-        D->states = nullptr;
-        D->slots = 0;
-        PP_HIP(hipMalloc(&D->states, 2 * sb * need_slots));  // both halves
-        D->slots = need_slots;
-    }
-    if (ns > D->ns_cap) {  // soff / slen / status share one capacity
-        int64_t c = 0;
-        D->ns_cap = 0;
-        PP_HIP(grow(&D->soff, &c, ns));
-        c = 0;
-        PP_HIP(grow(&D->slen, &c, ns));
-        c = 0;
-        PP_HIP(grow(&D->status, &c, ns));
-        D->ns_cap = ns;
-    }
-    PP_HIP(grow(&D->gop, &D->gop_cap, (int64_t)gop.size()));
-    for (int64_t k = 0, off = 0; k < n; off += (bytes[k] + 63) & ~int64_t(63), ++k)
-        if (bytes[k]) PP_HIP(hipMemcpyAsync(D->pkt + off, packets[k], bytes[k], hipMemcpyHostToDevice, st));
-    PP_HIP(hipMemcpyAsync(D->soff, soff.data(), sizeof(int64_t) * ns, hipMemcpyHostToDevice, st));
-    PP_HIP(hipMemcpyAsync(D->slen, slen.data(), sizeof(int64_t) * ns, hipMemcpyHostToDevice, st));
+    PP_HIP(grow(&D->pkt, &D->pkt_cap, P.total, P.total + 64));  // the bytestream window reads up to 8 B past a slice
+    PP_HIP(grow(&D->states, &D->slots, need_slots, 2 * sb * need_slots));  // both halves
+    PP_HIP(grow(&D->slices, &D->ns_cap, ns, (2 * sizeof(int64_t) + sizeof(int)) * ns));
+    PP_HIP(grow(&D->gop, &D->gop_cap, (int64_t)gop.size(), sizeof(int) * gop.size()));
+    int64_t *const d_soff = D->slices, *const d_slen = D->slices + ns;  // soff[ns] | slen[ns] | status[ns]
+    int *const d_status = reinterpret_cast<int *>(D->slices + 2 * ns);
+    for (int k = 0; k < n; ++k)
+        if (P.bytes[k]) PP_HIP(hipMemcpyAsync(D->pkt + P.base[k], packets[k], P.bytes[k], hipMemcpyHostToDevice, st));
+    PP_HIP(hipMemcpyAsync(d_soff, P.soff.data(), sizeof(int64_t) * ns, hipMemcpyHostToDevice, st));
+    PP_HIP(hipMemcpyAsync(d_slen, P.slen.data(), sizeof(int64_t) * ns, hipMemcpyHostToDevice, st));
     PP_HIP(hipMemcpyAsync(D->gop, gop.data(), sizeof(int) * gop.size(), hipMemcpyHostToDevice, st));
-    PP_HIP(hipMemsetAsync(D->status, 0, sizeof(int) * ns, st));
+    PP_HIP(hipMemsetAsync(d_status, 0, sizeof(int) * ns, st));
     const int64_t half = sb * D->slots, used = sb * need_slots;
     const int64_t chalf = sb * ((per + 63) / 64 * 64);
     PP_HIP(hipMemsetAsync(D->states, 128, used, st));
@@ -858,8 +765,9 @@ static int decode_group(pp_ffv1_dec *const *decs, int n, const uint8_t *const *p
     for (int k = 0; k < n; ++k)  // a stream whose first GOP continues its carried states
         if (ngop[k] && !gop[3 * first_gop[k] + 2])
             PP_HIP(copy_states(decs[k]->carry, chalf, 0, D->states, half, first_gop[k] * per));
+    // launch
     Ffv1DecArgs a{};
-    a.pkt = D->pkt; a.soff = D->soff; a.slen = D->slen;
+    a.pkt = D->pkt; a.soff = d_soff; a.slen = d_slen;
     for (int p = 0; p < 3; ++p) {
         a.dst[p] = static_cast<uint8_t *>(dst->data[p]);
         a.ls[p] = dst->linesize[p];
@@ -873,7 +781,7 @@ static int decode_group(pp_ffv1_dec *const *decs, int n, const uint8_t *const *p
         a.init_off[t] = t < R.ntables ? D->init_off[t] : -1;
     }
     a.state_bytes = sb;
-    a.states = D->states; a.cold = D->states + half; a.status = D->status; a.tables = D->tables; a.quant = D->dquant;
+    a.states = D->states; a.cold = D->states + half; a.status = d_status; a.tables = D->tables; a.quant = D->dquant;
     for (int k = 0; k < 5; ++k) a.qthr[k] = k < D->pq.n ? D->pq.thr[k] : 1024;
     a.init = D->dinit;
     // chains per workgroup: the LDS bound, spread over the CUs when chains are few (long GOPs)
@@ -905,8 +813,9 @@ static int decode_group(pp_ffv1_dec *const *decs, int n, const uint8_t *const *p
     // each stream's last GOP states, for its next decode that continues it
     for (int k = 0; k < n; ++k)
         if (ngop[k]) PP_HIP(copy_states(D->states, half, (first_gop[k] + ngop[k] - 1) * per, decs[k]->carry, chalf, 0));
+    // status
     std::vector<int> status(ns);
-    PP_HIP(hipMemcpyAsync(status.data(), D->status, sizeof(int) * ns, hipMemcpyDeviceToHost, st));
+    PP_HIP(hipMemcpyAsync(status.data(), d_status, sizeof(int) * ns, hipMemcpyDeviceToHost, st));
     PP_HIP(hipStreamSynchronize(st));
     static const char *what[] = {"ok", "slice CRC mismatch", "bad slice header", "bytestream end mismatch"};
     for (int64_t i = 0, fk = 0, k = 0; i < ns; ++i) {

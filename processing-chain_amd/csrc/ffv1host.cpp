@@ -1,12 +1,14 @@
 // Host side of the FFV1 codec: state tables, CRC, configuration record, slice
-// footers (see ffv1host.hpp).  The algorithms follow FFmpeg's ffv1enc.c /
-// ffv1dec.c / rangecoder.c as published (RFC 9043); no HIP here.
+// footers, the plan of a group decode (see ffv1host.hpp).  The algorithms
+// follow FFmpeg's ffv1enc.c / ffv1dec.c / rangecoder.c as published (RFC
+// 9043); no HIP here.
 #include "ffv1host.hpp"
 
 #include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <utility>
 
 #include "../../include/pixpath.h"
 
@@ -372,6 +374,46 @@ int ffv1_slice_table(const uint8_t *packets, const int64_t *frame_sizes, int nfr
         base += frame_sizes[f];
     }
     if (total) *total = base;
+    return PP_OK;
+}
+
+int ffv1_plan_group(int n, const uint8_t *const *packets, const int64_t *const *frame_sizes, const int *nframes,
+                    const char *carry_in, int per, int ec, Ffv1GroupPlan *plan, int *failed_stream, std::string *err) {
+    Ffv1GroupPlan P;
+    for (int k = 0; k < n; ++k) P.ftot += nframes[k];
+    P.soff.resize(P.ftot * per);
+    P.slen.resize(P.ftot * per);
+    P.first_gop.resize(n);
+    P.ngop.resize(n);
+    P.bytes.resize(n);
+    P.base.resize(n);
+    int64_t f0 = 0;
+    for (int k = 0; k < n; ++k) {  // slice tables and GOPs, stream by stream
+        *failed_stream = k;
+        const int64_t base = P.base[k] = P.total;
+        P.first_gop[k] = (int)P.gop.size() / 3;
+        const int nf = nframes[k];
+        if (nf == 0) continue;
+        if (int rc = ffv1_slice_table(packets[k], frame_sizes[k], nf, per, ec, P.soff.data() + f0 * per,
+                                      P.slen.data() + f0 * per, &P.bytes[k], err))
+            return rc;
+        for (int64_t i = f0 * per; i < (f0 + nf) * per; ++i) P.soff[i] += base;
+        for (int f = 0; f < nf; ++f) {  // a keyframe starts a GOP; frame 0 without one continues the carried one
+            const int64_t s0 = (f0 + f) * per;
+            const int key = ffv1_keyframe_bit(packets[k] + P.soff[s0] - base, P.slen[s0]);
+            if (f == 0 || key) {
+                if (f == 0 && !key && !carry_in[k])
+                    return fail(err, PP_ERR_INVALID, "frame 0 is not a keyframe and no earlier frame of its GOP "
+                                                     "was decoded");
+                P.gop.insert(P.gop.end(), {(int)(f0 + f), 0, key});
+            }
+            P.gop[P.gop.size() - 2]++;
+        }
+        P.ngop[k] = (int)P.gop.size() / 3 - P.first_gop[k];
+        P.total += (P.bytes[k] + 63) & ~int64_t(63);
+        f0 += nf;
+    }
+    *plan = std::move(P);
     return PP_OK;
 }
 

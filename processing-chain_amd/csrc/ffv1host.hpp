@@ -1,9 +1,11 @@
 // Host side of the FFV1 codec: the range-coder
 // state tables, the CRC, the configuration record (written by the encoder,
-// parsed and checked by the decoder) and the walk of a frame packet's slice
-// footers.  Plain C++ with no HIP dependency, so it also builds on its own
-// under ASan / UBSan (`make sanitize`, csrc/fuzz_host.cpp) and is fuzzed with
-// corrupt records and packets -- every byte it reads comes from a file.
+// parsed and checked by the decoder), the walk of a frame packet's slice
+// footers and the plan of a group decode (the tables the decode kernel
+// indexes unchecked).  Plain C++ with no HIP dependency, so it also builds on
+// its own under ASan / UBSan (`make sanitize`, csrc/fuzz_host.cpp) and is
+// fuzzed with corrupt records and packets -- every byte it reads comes from a
+// file.
 #pragma once
 
 #include <cstdint>
@@ -72,5 +74,27 @@ int ffv1_keyframe_bit(const uint8_t *slice0, int64_t n);
 // slen bytes (footer included).  0, or a negative PP_ERR_* with *err set.
 int ffv1_slice_table(const uint8_t *packets, const int64_t *frame_sizes, int nframes, int per, int ec,
                      int64_t *soff, int64_t *slen, int64_t *total, std::string *err);
+
+// What one decode launch over n streams of one configuration record reads from
+// the host: the tables ffv1_decode_kernel indexes unchecked.  Stream k's
+// packets sit at base[k] of one packet buffer, 64-byte aligned, in stream
+// order; its frames follow those of the streams before it.
+struct Ffv1GroupPlan {
+    int64_t ftot = 0, total = 0;      // frames over all streams; packet-buffer bytes (the 64-B padded streams)
+    std::vector<int64_t> soff, slen;  // [ftot * per] slice start in the packet buffer, length (footer included)
+    std::vector<int> gop;             // [ngops][3]: first frame, frames, 1 = starts at a keyframe (else carried states)
+    std::vector<int> first_gop, ngop; // per stream: its GOPs in `gop`
+    std::vector<int64_t> bytes, base; // per stream: packet bytes, start in the packet buffer
+};
+
+// Plan the decode of n streams (stream k: nframes[k] packets back to back at
+// packets[k], frame_sizes[k] bytes each; carry_in[k]: the states of the GOP
+// its frame 0 may continue are at hand).  Each stream's slice table, then its
+// GOPs: a keyframe (ffv1_keyframe_bit) starts one, frame 0 without one
+// continues the carried GOP.  0, or a negative PP_ERR_* with *failed_stream
+// and *err (no stream prefix) set; streams are planned in order, so those
+// after the failed one were not looked at.
+int ffv1_plan_group(int n, const uint8_t *const *packets, const int64_t *const *frame_sizes, const int *nframes,
+                    const char *carry_in, int per, int ec, Ffv1GroupPlan *plan, int *failed_stream, std::string *err);
 
 }  // namespace pp

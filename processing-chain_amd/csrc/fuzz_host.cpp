@@ -20,7 +20,15 @@
 //   * the scaler planner (scale_plan.cpp): plain and chain layouts of the
 //     tested shapes and of seeded random ones, bound to their own table blob
 //     and walked the way scale_kernel / strip_kernel index them -- every
-//     window, ring row, staged row and LDS byte inside what the layout sizes.
+//     window, ring row, staged row and LDS byte inside what the layout sizes;
+//   * the group decode planner (ffv1host.cpp ffv1_plan_group): groups of 1-6
+//     streams of 0-40 frames with random slice counts, keyframes and carried
+//     GOPs, half of them valid, half with mutated packets or frame sizes --
+//     an accepted plan is read as decode_group's uploads and
+//     ffv1_decode_kernel read it: every slice inside its stream's 64-byte
+//     aligned window of the packet buffer, the GOP triples tiling the frames
+//     stream by stream, a continued GOP only where states were carried; a
+//     refused one names its stream and says why.
 //
 //   * general FFV1 records given as seeds (file of u32-LE-length-prefixed
 //     records: the oracle's FFmpeg-like records with transmitted state
@@ -607,6 +615,169 @@ long fuzz_plans(Rng &r, int iters) {
     return n;
 }
 
+// ---- group decode plans (ffv1host.cpp ffv1_plan_group) ------------------------
+struct GroupCase {
+    int n, per, ec;
+    std::vector<std::vector<uint8_t>> pk;     // per stream: its packets back to back
+    std::vector<std::vector<int64_t>> sizes;  // per stream: frame sizes
+    std::vector<int> nframes;
+    std::vector<char> carry;
+    long gops = 0;  // GOPs the frames were built with
+};
+
+// a group of valid streams: slices with 24-bit size footers, keyframes placed
+// at random (a frame 0 that continues a GOP only where carry is set)
+GroupCase make_group(Rng &r) {
+    static const int pers[] = {1, 4, 6, 16, 64};
+    GroupCase g;
+    g.n = 1 + r.below(6);
+    g.per = pers[r.below(5)];
+    g.ec = r.below(2);
+    g.pk.resize(g.n);
+    g.sizes.resize(g.n);
+    for (int k = 0; k < g.n; ++k) {
+        const int nf = r.below(41);
+        g.nframes.push_back(nf);
+        g.carry.push_back((char)r.below(2));
+        for (int f = 0; f < nf; ++f) {
+            const bool key = f == 0 && !g.carry[k] ? true : r.below(4) == 0;
+            g.gops += f == 0 || key;
+            const size_t base = g.pk[k].size();
+            for (int s = 0; s < g.per; ++s) {
+                const int len = 2 + r.below(12);
+                for (int i = 0; i < len; ++i) g.pk[k].push_back((uint8_t)r.next());
+                if (s == 0) {  // the keyframe bit: the first two bytes against 0x7F80 (ffv1_keyframe_bit)
+                    uint8_t *b = g.pk[k].data() + g.pk[k].size() - len;
+                    if (r.below(4) == 0) {
+                        b[0] = 0x7F;
+                        b[1] = (uint8_t)((key ? 0x80 : 0) | (b[1] & 0x7F));
+                    } else {
+                        b[0] = (uint8_t)(key ? 0x80 | b[0] : b[0] % 0x7F);
+                    }
+                }
+                g.pk[k].push_back((uint8_t)(len >> 16));
+                g.pk[k].push_back((uint8_t)(len >> 8));
+                g.pk[k].push_back((uint8_t)len);
+                for (int i = 0; i < 5 * g.ec; ++i) g.pk[k].push_back((uint8_t)r.next());
+            }
+            g.sizes[k].push_back((int64_t)(g.pk[k].size() - base));
+        }
+    }
+    return g;
+}
+
+// an accepted plan, checked the way decode_group's uploads and
+// ffv1_decode_kernel read it
+void check_group(const GroupCase &g, const std::vector<const uint8_t *> &pk, const Ffv1GroupPlan &P, long id) {
+    char tag[48];
+    std::snprintf(tag, sizeof tag, "group %ld", id);
+    const int n = g.n, per = g.per;
+    int64_t ftot = 0;
+    for (int nf : g.nframes) ftot += nf;
+    const int fail0 = g_fail;  // a table that failed a check is not indexed further
+    PCHECK(P.ftot == ftot && P.soff.size() == (size_t)(ftot * per) && P.slen.size() == P.soff.size() &&
+               P.gop.size() % 3 == 0 && P.first_gop.size() == (size_t)n && P.ngop.size() == (size_t)n &&
+               P.bytes.size() == (size_t)n && P.base.size() == (size_t)n,
+           "table sizes for %lld frames", (long long)ftot);
+    if (g_fail != fail0) return;
+    const int ngops = (int)P.gop.size() / 3;
+    int64_t at = 0, f0 = 0;  // packet-buffer bytes and frames of the streams so far
+    int g0 = 0;              // their GOPs
+    for (int k = 0; k < n; ++k) {
+        const int nf = g.nframes[k];
+        int64_t sum = 0;
+        for (int64_t s : g.sizes[k]) sum += s;
+        PCHECK(P.base[k] == at && at % 64 == 0 && P.bytes[k] == sum, "stream %d window [%lld, +%lld), expected [%lld, +%lld)",
+               k, (long long)P.base[k], (long long)P.bytes[k], (long long)at, (long long)sum);
+        for (int64_t i = f0 * per; i < (f0 + nf) * per; ++i)
+            PCHECK(P.base[k] <= P.soff[i] && P.slen[i] >= 0 && P.soff[i] + P.slen[i] <= P.base[k] + P.bytes[k],
+                   "stream %d slice %lld [%lld, +%lld) outside its window", k, (long long)i, (long long)P.soff[i],
+                   (long long)P.slen[i]);
+        PCHECK(P.first_gop[k] == g0 && P.ngop[k] >= 0 && g0 + P.ngop[k] <= ngops && (nf > 0) == (P.ngop[k] > 0),
+               "stream %d GOPs [%d, +%d) after %d of %d", k, P.first_gop[k], P.ngop[k], g0, ngops);
+        if (g_fail != fail0) return;
+        int64_t f = f0;
+        for (int q = g0; q < g0 + P.ngop[k]; ++q) {  // the stream's GOPs tile its frames
+            const int first = P.gop[3 * q], cnt = P.gop[3 * q + 1], flag = P.gop[3 * q + 2];
+            PCHECK(first == f && cnt >= 1 && f + cnt <= f0 + nf, "GOP %d frames [%d, +%d) at %lld of stream %d to %lld", q,
+                   first, cnt, (long long)f, k, (long long)(f0 + nf));
+            PCHECK(flag == 1 || (flag == 0 && q == g0 && g.carry[k]), "GOP %d flag %d (stream %d, carry %d)", q, flag, k,
+                   g.carry[k]);
+            if (g_fail != fail0) return;
+            for (int j = 0; j < cnt; ++j) {  // the flag is the first frame's keyframe bit; no keyframe inside a GOP
+                const int64_t s0 = (f + j) * per;
+                const int key = ffv1_keyframe_bit(pk[k] + (P.soff[s0] - P.base[k]), P.slen[s0]);
+                PCHECK(key == (j == 0 ? flag : 0), "GOP %d frame %d keyframe bit %d", q, j, key);
+            }
+            f += cnt;
+        }
+        PCHECK(f == f0 + nf, "stream %d GOPs end at frame %lld of %lld", k, (long long)f, (long long)(f0 + nf));
+        at += (sum + 63) & ~int64_t(63);
+        f0 += nf;
+        g0 += P.ngop[k];
+    }
+    PCHECK(g0 == ngops && P.total == at, "%d GOPs of %d, buffer %lld of %lld", g0, ngops, (long long)P.total, (long long)at);
+}
+
+// The first half of the groups are valid and must plan, to the GOPs they were
+// built with; the second half have a stream's packets or frame sizes mutated,
+// or a frame 0 turned into an inter frame.
+long fuzz_groups(Rng &r, int iters, long *ok) {
+    long n = 0;
+    for (int it = 0; it < iters; ++it) {
+        GroupCase g = make_group(r);
+        const bool valid = it < (iters + 1) / 2;
+        if (!valid) {
+            const int k = r.below(g.n), kind = r.below(3);
+            std::vector<uint8_t> &b = g.pk[k];
+            std::vector<int64_t> &sz = g.sizes[k];
+            if (kind == 0) {
+                mutate(r, b);
+            } else if (kind == 1 && !sz.empty()) {
+                std::vector<uint8_t> raw(sz.size() * 8);
+                std::memcpy(raw.data(), sz.data(), raw.size());
+                mutate(r, raw);
+                std::memcpy(sz.data(), raw.data(), std::min(raw.size(), sz.size() * 8));
+            } else if (b.size() >= 2) {
+                b[0] = 0;
+            }
+            // a caller hands over a buffer of the sizes it claims: sizes past the
+            // bytes that are left are cut to them, up to the first negative one
+            // (which must be refused before anything behind it is read)
+            int64_t tot = 0;
+            for (auto &s : sz) {
+                if (s < 0) break;
+                s = std::min<int64_t>(s, (int64_t)b.size() - tot);
+                tot += s;
+            }
+        }
+        std::vector<std::vector<uint8_t>> held;
+        std::vector<const uint8_t *> pk;
+        std::vector<const int64_t *> sz;
+        for (int k = 0; k < g.n; ++k) {
+            held.push_back(exact(g.pk[k]));
+            pk.push_back(held.back().data());
+            sz.push_back(g.sizes[k].data());
+        }
+        Ffv1GroupPlan P;
+        std::string err;
+        int failed = -1;
+        const int rc = ffv1_plan_group(g.n, pk.data(), sz.data(), g.nframes.data(), g.carry.data(), g.per, g.ec, &P,
+                                       &failed, &err);
+        ++n;
+        if (rc == 0) {
+            ++*ok;
+            check_group(g, pk, P, n);
+            if (valid) CHECK((long)P.gop.size() / 3 == g.gops, "group %ld: %zu GOPs planned, %ld built", n, P.gop.size() / 3, g.gops);
+        } else {
+            CHECK(!valid, "group %ld: a valid group was refused: %s", n, err.c_str());
+            CHECK(rc < 0 && failed >= 0 && failed < g.n && !err.empty(), "group %ld: failure %d at stream %d, message '%s'", n,
+                  rc, failed, err.c_str());
+        }
+    }
+    return n;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -619,7 +790,9 @@ int main(int argc, char **argv) {
     const long d = fuzz_filters(r, iters / 20);
     const long e = argc > 3 ? fuzz_seed_records(r, iters, argv[3]) : 0;
     const long f = fuzz_plans(r, iters / 60);
-    std::printf("records %ld packets %ld scans %ld filters %ld seeded %ld plans %ld failures %d\n", a, b, c, d, e, f,
-                g_fail);
+    long groups_ok = 0;
+    const long g = fuzz_groups(r, iters / 10, &groups_ok);
+    std::printf("records %ld packets %ld scans %ld filters %ld seeded %ld plans %ld groups %ld groups_ok %ld failures %d\n",
+                a, b, c, d, e, f, g, groups_ok, g_fail);
     return g_fail ? 1 : 0;
 }
