@@ -189,6 +189,24 @@ int pp_siti_ex(pp_ctx *ctx, int bitdepth, int w, int h, const void *luma,
                int64_t linesize, int64_t frame_stride, int nframes,
                const void *prev, double *si, double *ti, int flags, void *stream);
 
+/* ---- full-reference PSNR / SSIM (spec PP-METRIC-1) --------
+ * New feature after p03_generateAvPvs.py: how far an AVPVS is from its SRC,
+ * per frame and plane (the reference's image builds FFmpeg with libvmaf for
+ * this step).  Modelled on vf_psnr / vf_ssim; parity with FFmpeg is unpinned.
+ * ref, dist: batches of w x h frames of the planar format `fmt` (packed
+ * formats: PP_ERR_INVALID); pitches and frame strides may differ.  dist frame
+ * k is compared with ref frame ref_index[k] (HOST array of nframes entries,
+ * NULL = identity; a negative entry is PP_ERR_INVALID).  sse / ssim: DEVICE
+ * arrays of nframes x 3, frame-major: the exact sum of squared differences of
+ * every sample of the plane, and the mean SSIM over its 8x8 windows at stride
+ * 4 (NaN for a plane under 8 samples wide or high).  Arguments are checked
+ * before any HIP call.  The partials workspace belongs to the context.
+ * Added without raising PP_ABI_VERSION (still 7): the addition is backward
+ * compatible, no existing entry point or structure changed. */
+int pp_metrics(pp_ctx *ctx, int fmt, int w, int h, const pp_frames *ref,
+               const pp_frames *dist, const int32_t *ref_index, int nframes,
+               uint64_t *sse, double *ssim, void *stream);
+
 /* ---- host helpers --------------------------------------------------------
  * vf_fps output->input frame map (lib/ffmpeg.py:832-834, :959-961, :1038,
  * :1179): map[k] = input frame shown at output frame k.  Returns the number of

@@ -109,6 +109,9 @@ struct Ctx {
     // spinner animation (PP-STALL-1), device resident
     int spin_fmt = -1, spin_n = 0, spin_w = 0, spin_h = 0;
     void *spin_buf = nullptr; // [n][Y(w*h) A(w*h) U V Ac (cw*ch each)] uint16
+    // pp_metrics partials (PP-METRIC-1), grown on demand
+    void *met_buf = nullptr;
+    size_t met_cap = 0;
 };
 
 } // namespace pp

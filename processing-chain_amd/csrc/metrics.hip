@@ -1,0 +1,360 @@
+// Full-reference PSNR / SSIM of two frame batches (spec PP-METRIC-1)
+// on gfx950.
+//
+// New feature after p03 (the reference's image builds FFmpeg with libvmaf for
+// this step; it has no code of its own).  Modelled on FFmpeg's vf_psnr and
+// vf_ssim (x264's 4x4-block / 8x8-window SSIM at stride 4), parity unpinned.
+//
+//   SSE  = sum (a - b)^2 over every sample of a plane             (uint64)
+//   SSIM = mean over the (bw-1)(bh-1) windows of 2x2 blocks of
+//          (2 s1 s2 + c1)(2 covar + c2) / ((s1^2 + s2^2 + c1)(vars + c2))
+//
+// Layout: a workgroup (256 lanes, 4 waves) owns one unit = (frame, plane,
+// column span, band of kBandBlocks block rows).  A lane takes 16 B of a row
+// from each input (8 samples at 10 bits = 2 blocks, 16 at 8 bits = 4 blocks)
+// through bounds-checked buffer loads and builds its 4x4 block sums
+// (s1, s2, ss, s12) over four rows with v_dot2 / v_dot4.  The right-hand
+// neighbour block comes from the next lane by a DPP wave shift; lane 63 of
+// every wave is a halo lane that loads the 16 B right of the wave's span (a
+// second read served by the caches) and owns nothing.  The horizontal block
+// pairs of the previous block row stay in registers for the vertical half of
+// the window, so a band reads every sample once plus one halo block row below.
+// Samples outside the plane read as 0 in BOTH inputs (buffer range for rows
+// and whole lanes, a mask for the lane straddling a ragged right edge), so
+// the block identity ss - 2 s12 = sum (a - b)^2 gives the SSE of partial
+// blocks too: the trailing pw & 3 columns and ph & 3 rows count in the SSE
+// and never complete a window.
+// Integers: block and window sums fit 32 bits (a window's ss <= 64 * 2 *
+// 1023^2 < 2^28); vars and covar are formed in 64 bits (64 ss, s1^2 and
+// 2 s1 s2 pass 2^31 at 10 bits) and every quotient is fp64.
+// Reduction: lane -> wave (xor butterfly) -> workgroup (4 values through LDS
+// in wave order) -> one partial per unit, no atomics; metrics_finalize adds a
+// (frame, plane)'s partials in unit order: bit-reproducible.
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+
+#include "common.hpp"
+#include "device.hpp"
+
+namespace pp {
+
+constexpr int kMetLaneBytes = 16;   // one load per lane and row
+constexpr int kMetOwnLanes = 63;    // lanes of a wave that own blocks; lane 63 is the halo lane
+constexpr int kMetWaves = 4;        // waves per workgroup
+constexpr int kBandBlocks = 16;     // block rows per band (64 sample rows), plus one halo block row
+constexpr int kMetIdx = 256;        // ref_index entries per launch (kernel arguments)
+
+struct MetPartial {
+    uint64_t sse;
+    double ssim;  // sum of the unit's window values
+};
+
+struct MetArgs {
+    const uint8_t *ref[3], *dist[3];
+    int64_t rls[3], rfs[3], dls[3], dfs[3];
+    int pw[3], ph[3];
+    int tiles_x[3], tile0[3];  // column spans of a plane; first tile of a plane within a frame
+    int tiles;                 // tiles of one frame (all planes)
+    int nk;                    // dist frames of this launch
+    int identity;              // ref frame = dist frame (idx unused)
+    int depth;
+    MetPartial *part;          // [nk][tiles]
+    int32_t idx[kMetIdx];
+};
+
+template <typename T>
+__device__ inline uint32_t dot(uint32_t a, uint32_t b, uint32_t acc) {
+    typedef uint16_t v2u16 __attribute__((ext_vector_type(2)));
+    if constexpr (sizeof(T) == 2)
+        return __builtin_amdgcn_udot2(__builtin_bit_cast(v2u16, a), __builtin_bit_cast(v2u16, b), acc, false);
+    else
+        return __builtin_amdgcn_udot4(a, b, acc, false);
+}
+
+// Four rows x 16 B of one input.
+struct Quad {
+    uint32_t w[4][4];
+};
+
+// Rows r0..r0+3 of a plane at lane byte offset voff (kOob for a lane right of
+// the plane).  ALIGNED: one 16-B buffer load a row; rows >= ph lie past the
+// descriptor's range and read 0.  Otherwise sample by sample with explicit
+// bounds (pointers or pitches off the 16-B grid).
+template <typename T, bool ALIGNED>
+__device__ inline void load_quad(Quad &q, const uint8_t *base, __amdgpu_buffer_rsrc_t rs, uint32_t voff, uint32_t ls,
+                                 int r0, int x, int pw, int ph) {
+    if constexpr (ALIGNED) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const auto v = __builtin_amdgcn_raw_buffer_load_b128(rs, voff + (uint32_t)(r0 + j) * ls, 0, 0);
+            __builtin_memcpy(q.w[j], &v, 16);
+        }
+    } else {
+        constexpr int SPD = 4 / sizeof(T);  // samples per dword
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            // every load goes to a sample of the plane (clamped); the select drops the others
+            const T *row = reinterpret_cast<const T *>(base + (int64_t)min(r0 + j, ph - 1) * ls);
+            const bool row_in = r0 + j < ph;
+#pragma unroll
+            for (int d = 0; d < 4; ++d) {
+                uint32_t v = 0;
+#pragma unroll
+                for (int e = 0; e < SPD; ++e) {
+                    const int xe = x + d * SPD + e;
+                    const uint32_t s = row[min(xe, pw - 1)];
+                    v |= ((row_in && xe < pw) ? s : 0u) << (8 * sizeof(T) * e);
+                }
+                q.w[j][d] = v;
+            }
+        }
+    }
+}
+
+// One window from its exact sums; widened before multiplying (PP-METRIC-1).
+__device__ inline double ssim_window(uint32_t s1, uint32_t s2, uint32_t ss, uint32_t s12, double c1, double c2) {
+    const int64_t a = s1, b = s2;
+    const int64_t sq = a * a + b * b;
+    const int64_t vars = 64 * (int64_t)ss - sq;
+    const int64_t covar = 64 * (int64_t)s12 - a * b;
+    const double num = ((double)(2 * a * b) + c1) * ((double)(2 * covar) + c2);
+    const double den = ((double)sq + c1) * ((double)vars + c2);
+    return num / den;
+}
+
+template <typename T, bool ALIGNED, bool RAGGED>
+__device__ __forceinline__ void metrics_unit(const MetArgs &a, int k, int tile, MetPartial *out) {
+    constexpr int PX = kMetLaneBytes / sizeof(T);  // samples per lane and row
+    constexpr int LB = PX / 4;                     // blocks per lane
+    constexpr int DPB = 4 / LB;                    // dwords per block row of a block
+    constexpr int SPD = 4 / sizeof(T);
+    constexpr uint32_t kOnes = sizeof(T) == 2 ? 0x00010001u : 0x01010101u;
+    __shared__ uint64_t s_sse[kMetWaves];
+    __shared__ double s_ssim[kMetWaves];
+
+    const int p = tile >= a.tile0[2] ? 2 : tile >= a.tile0[1] ? 1 : 0;
+    const int t = tile - a.tile0[p];
+    const int tx = t % a.tiles_x[p], band = t / a.tiles_x[p];
+    const int pw = a.pw[p], ph = a.ph[p];
+    const int bw = pw >> 2, bh = ph >> 2, bhc = (ph + 3) >> 2;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int x = ((tx * kMetWaves + wave) * kMetOwnLanes + lane) * PX;
+    const bool own = lane < kMetOwnLanes;
+    const int c0 = x >> 2;  // the lane's first block column
+    const int b0 = band * kBandBlocks;
+
+    const int rf = a.identity ? k : a.idx[k];
+    const uint8_t *rbase = a.ref[p] + (int64_t)rf * a.rfs[p];
+    const uint8_t *dbase = a.dist[p] + (int64_t)k * a.dfs[p];
+    const uint32_t rls = (uint32_t)a.rls[p], dls = (uint32_t)a.dls[p];
+    // a row load straddling num_records reads 0 as a whole: the last row counts
+    // up to its 16-B-rounded width, which lies inside the (aligned) pitch
+    const int64_t wb = ((int64_t)pw * sizeof(T) + 15) & ~int64_t(15);
+    const auto rrs = uniform_rsrc(rbase, ALIGNED ? (int)((int64_t)(ph - 1) * a.rls[p] + min(a.rls[p], wb)) : 0);
+    const auto drs = uniform_rsrc(dbase, ALIGNED ? (int)((int64_t)(ph - 1) * a.dls[p] + min(a.dls[p], wb)) : 0);
+    const uint32_t voff = x < pw ? (uint32_t)(x * (int)sizeof(T)) : (uint32_t)kOobOff;
+
+    uint32_t mask[4];  // RAGGED: the samples of the lane inside the plane
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+        uint32_t m = 0;
+#pragma unroll
+        for (int e = 0; e < SPD; ++e)
+            if (x + d * SPD + e < pw) m |= (sizeof(T) == 2 ? 0xffffu : 0xffu) << (8 * sizeof(T) * e);
+        mask[d] = m;
+    }
+    const double mx = (double)((1 << a.depth) - 1);
+    const double c1 = .01 * .01 * mx * mx * 64.0, c2 = .03 * .03 * mx * mx * 64.0 * 63.0;
+
+    uint32_t sse = 0;   // <= 16 block rows * 32 samples * 1023^2 < 2^32
+    double acc = 0.0;
+    uint32_t prev[LB][4];  // horizontal block pairs of the block row above
+    Quad qa, qb;
+    load_quad<T, ALIGNED>(qa, rbase, rrs, voff, rls, 4 * b0, x, pw, ph);
+    load_quad<T, ALIGNED>(qb, dbase, drs, voff, dls, 4 * b0, x, pw, ph);
+    // block row i of the band (kBandBlocks is the halo block row)
+    auto step = [&](int i) {
+        Quad ca = qa, cb = qb;
+        if (i < kBandBlocks) {  // the next block row travels while this one is summed
+            load_quad<T, ALIGNED>(qa, rbase, rrs, voff, rls, 4 * (b0 + i + 1), x, pw, ph);
+            load_quad<T, ALIGNED>(qb, dbase, drs, voff, dls, 4 * (b0 + i + 1), x, pw, ph);
+        }
+        uint32_t blk[LB + 1][4];
+#pragma unroll
+        for (int b = 0; b < LB; ++b) {
+            uint32_t s1 = 0, s2 = 0, ss = 0, s12 = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int d = b * DPB; d < (b + 1) * DPB; ++d) {
+                    uint32_t va = ca.w[j][d], vb = cb.w[j][d];
+                    if constexpr (RAGGED && ALIGNED) { va &= mask[d]; vb &= mask[d]; }
+                    s1 = dot<T>(va, kOnes, s1);
+                    s2 = dot<T>(vb, kOnes, s2);
+                    ss = dot<T>(va, va, ss);
+                    ss = dot<T>(vb, vb, ss);
+                    s12 = dot<T>(va, vb, s12);
+                }
+            blk[b][0] = s1; blk[b][1] = s2; blk[b][2] = ss; blk[b][3] = s12;
+            if (i < kBandBlocks) sse += ss - 2 * s12;  // sum (a - b)^2 of the block; the halo row belongs to the next band
+        }
+        // the next lane's first block (wave_shl:1; the halo lane's own result is unused)
+#pragma unroll
+        for (int v = 0; v < 4; ++v)
+            blk[LB][v] = (uint32_t)__builtin_amdgcn_mov_dpp((int)blk[0][v], 0x130, 0xf, 0xf, true);
+        const bool rows_ok = b0 + i < bh;  // the lower block row of the window is a full one
+#pragma unroll
+        for (int b = 0; b < LB; ++b) {
+            uint32_t h[4];
+#pragma unroll
+            for (int v = 0; v < 4; ++v) h[v] = blk[b][v] + blk[b + 1][v];
+            if (i > 0 && own && rows_ok && c0 + b + 1 < bw)
+                acc += ssim_window(prev[b][0] + h[0], prev[b][1] + h[1], prev[b][2] + h[2], prev[b][3] + h[3], c1, c2);
+#pragma unroll
+            for (int v = 0; v < 4; ++v) prev[b][v] = h[v];
+        }
+    };
+    // rows at and below bhc hold nothing but zeros (the test is uniform)
+    if constexpr (ALIGNED) {
+#pragma unroll
+        for (int i = 0; i <= kBandBlocks; ++i) {
+            if (b0 + i >= bhc) break;
+            step(i);
+        }
+    } else {  // the sample-by-sample path stays rolled: unrolled it spills SGPRs
+#pragma unroll 1
+        for (int i = 0; i <= kBandBlocks && b0 + i < bhc; ++i) step(i);
+    }
+
+    uint64_t s64 = own ? sse : 0;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        s64 += __shfl_xor(s64, o, 64);
+        acc += __shfl_xor(acc, o, 64);
+    }
+    __syncthreads();  // the previous unit's partial has been read
+    if (lane == 0) { s_sse[wave] = s64; s_ssim[wave] = acc; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        out->sse = s_sse[0] + s_sse[1] + s_sse[2] + s_sse[3];
+        out->ssim = ((s_ssim[0] + s_ssim[1]) + s_ssim[2]) + s_ssim[3];
+    }
+}
+
+// 1-D grid over the (frame, tile) units, frame-major and band-major within a
+// plane, with the XCD-aware numbering: the workgroups running at any moment
+// hold vertically adjacent bands of the same frames on one XCD, so a band's
+// halo block row is read from HBM by one neighbour and hits that L2 for the other.
+template <typename T, bool ALIGNED, bool RAGGED>
+__global__ __launch_bounds__(256) void metrics_kernel(const MetArgs a) {
+    const int64_t total = (int64_t)a.nk * a.tiles;
+    for (int64_t u = xcd_remap(blockIdx.x, gridDim.x); u < total; u += gridDim.x) {
+        const int k = (int)(u / a.tiles);
+        metrics_unit<T, ALIGNED, RAGGED>(a, k, (int)(u - (int64_t)k * a.tiles), a.part + u);
+    }
+}
+
+struct MetFinal {
+    int tile0[3], ntile[3];
+    int tiles;
+    int64_t windows[3];  // 0: SSIM undefined (bw < 2 or bh < 2)
+};
+
+// One lane per (frame, plane): its partials in unit order.
+__global__ __launch_bounds__(64) void metrics_finalize(const MetPartial *part, MetFinal f, int nframes, uint64_t *sse,
+                                                       double *ssim) {
+    const int o = blockIdx.x * 64 + threadIdx.x;
+    if (o >= nframes * 3) return;
+    const int k = o / 3, p = o - 3 * k;
+    const MetPartial *q = part + (int64_t)k * f.tiles + f.tile0[p];
+    uint64_t s = 0;
+    double v = 0.0;
+    for (int i = 0; i < f.ntile[p]; ++i) { s += q[i].sse; v += q[i].ssim; }
+    sse[o] = s;
+    ssim[o] = f.windows[p] ? v / (double)f.windows[p] : __builtin_nan("");
+}
+
+}  // namespace pp
+
+using namespace pp;
+
+extern "C" int pp_metrics(pp_ctx *ctx, int fmt, int w, int h, const pp_frames *ref, const pp_frames *dist,
+                          const int32_t *ref_index, int nframes, uint64_t *sse, double *ssim, void *stream) {
+    if (!ctx || !ref || !dist || !sse || !ssim) PP_FAIL(PP_ERR_INVALID, "null argument");
+    const FmtInfo fi = fmt_info(fmt);
+    if (!fi.valid || fi.packed) PP_FAIL(PP_ERR_INVALID, "metrics need a planar format (got %d)", fmt);
+    if (w < 1 || h < 1) PP_FAIL(PP_ERR_INVALID, "frame %dx%d", w, h);
+    if (nframes < 1) PP_FAIL(PP_ERR_INVALID, "nframes %d < 1", nframes);
+    if (ref_index)
+        for (int k = 0; k < nframes; ++k)
+            if (ref_index[k] < 0) PP_FAIL(PP_ERR_INVALID, "ref_index[%d] = %d is negative", k, ref_index[k]);
+    const int bytes = fi.depth > 8 ? 2 : 1;
+    const int span = kMetWaves * kMetOwnLanes * (kMetLaneBytes / bytes);
+    MetArgs a{};
+    MetFinal f{};
+    bool aligned = true, ragged = false;
+    for (int p = 0; p < 3; ++p) {
+        const int pw = p ? ceil_rshift(w, fi.hsub) : w, ph = p ? ceil_rshift(h, fi.vsub) : h;
+        const pp_frames *both[2] = {ref, dist};
+        for (const pp_frames *fr : both) {
+            const int64_t ls = fr->linesize[p], fs = fr->frame_stride[p];
+            if (!fr->data[p] || ls < (int64_t)pw * bytes) PP_FAIL(PP_ERR_INVALID, "plane %d: null data or short linesize", p);
+            if (((uintptr_t)fr->data[p] | (uint64_t)ls | (uint64_t)fs) & (bytes - 1))
+                PP_FAIL(PP_ERR_INVALID, "plane %d: 16-bit samples off the 2-byte grid", p);
+            // lane offsets and the band's halo rows stay inside the 31-bit buffer range
+            if ((int64_t)(ph + 4 * (kBandBlocks + 1)) * ls >= (int64_t)kOobOff)
+                PP_FAIL(PP_ERR_UNSUPPORTED, "plane %d of %lld bytes exceeds the 2 GiB buffer range", p, (long long)(ph * ls));
+            aligned &= !(((uintptr_t)fr->data[p] | (uint64_t)ls | (uint64_t)fs) & 15);
+        }
+        ragged |= (pw % (kMetLaneBytes / bytes)) != 0;
+        a.ref[p] = static_cast<const uint8_t *>(ref->data[p]);
+        a.dist[p] = static_cast<const uint8_t *>(dist->data[p]);
+        a.rls[p] = ref->linesize[p]; a.rfs[p] = ref->frame_stride[p];
+        a.dls[p] = dist->linesize[p]; a.dfs[p] = dist->frame_stride[p];
+        a.pw[p] = pw; a.ph[p] = ph;
+        a.tiles_x[p] = (pw + span - 1) / span;
+        const int bands = (((ph + 3) >> 2) + kBandBlocks - 1) / kBandBlocks;
+        a.tile0[p] = f.tile0[p] = a.tiles;
+        f.ntile[p] = a.tiles_x[p] * bands;
+        a.tiles += f.ntile[p];
+        const int bw = pw >> 2, bh = ph >> 2;
+        f.windows[p] = bw < 2 || bh < 2 ? 0 : (int64_t)(bw - 1) * (bh - 1);
+    }
+    f.tiles = a.tiles;
+    a.depth = fi.depth;
+
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    PP_HIP(hipSetDevice(ctx->device));
+    const size_t need = sizeof(MetPartial) * (size_t)a.tiles * nframes;
+    if (need > ctx->met_cap) {  // grown on demand, kept by the context (hipFree waits for earlier users)
+        if (ctx->met_buf) PP_HIP(hipFree(ctx->met_buf));
+        ctx->met_buf = nullptr; ctx->met_cap = 0;
+        PP_HIP(hipMalloc(&ctx->met_buf, need));
+        ctx->met_cap = need;
+    }
+    MetPartial *part = static_cast<MetPartial *>(ctx->met_buf);
+
+    using KFn = void (*)(const MetArgs);
+    const KFn k = bytes == 2 ? (!aligned ? metrics_kernel<uint16_t, false, true>
+                                         : ragged ? metrics_kernel<uint16_t, true, true> : metrics_kernel<uint16_t, true, false>)
+                             : (!aligned ? metrics_kernel<uint8_t, false, true>
+                                         : ragged ? metrics_kernel<uint8_t, true, true> : metrics_kernel<uint8_t, true, false>);
+    // identity: one launch over all frames; a map travels in the kernel
+    // arguments, kMetIdx dist frames per launch (as pp_stall_compose's)
+    const int per = ref_index ? kMetIdx : nframes;
+    for (int k0 = 0; k0 < nframes; k0 += per) {
+        MetArgs b = a;
+        b.nk = std::min(per, nframes - k0);
+        b.identity = ref_index == nullptr;
+        if (ref_index) std::memcpy(b.idx, ref_index + k0, sizeof(int32_t) * b.nk);
+        for (int p = 0; p < 3; ++p) b.dist[p] += (int64_t)k0 * a.dfs[p];
+        b.part = part + (int64_t)k0 * a.tiles;
+        const int64_t units = (int64_t)b.nk * a.tiles;
+        const int groups = (int)std::min<int64_t>(units, (int64_t)std::max(1, ctx->cus) * 8);
+        hipLaunchKernelGGL(k, dim3(groups), dim3(256), 0, st, b);
+    }
+    hipLaunchKernelGGL(metrics_finalize, dim3((nframes * 3 + 63) / 64), dim3(64), 0, st, part, f, nframes, sse, ssim);
+    PP_HIP(hipGetLastError());
+    return PP_OK;
+}

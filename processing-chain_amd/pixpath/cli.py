@@ -13,6 +13,7 @@ the ffmpeg strings they replace).
   concat long-test segment AVIs -> one AVI, packets copied (create_avpvs_long_concat :1058, GPU-FFV1 AVIs)
   preview AVPVS decoded here (GPU FFV1) -> ffmpeg's ProRes (create_preview :1250)
   siti   P.910 SI/TI of a SRC (util/SRC_analysis.py hook)
+  metrics per-frame PSNR / SSIM of a PVS against its SRC (spec PP-METRIC-1; after p03)
 
 Inputs/outputs ending in .y4m or .raw/.yuv are read/written directly;
 anything else goes through ffmpeg pipes.  The device is PIXPATH_DEVICE, else
@@ -636,6 +637,13 @@ def cmd_siti(args):
     return 0
 
 
+def cmd_metrics(args):
+    from . import metrics
+    res = metrics.metrics_of_files(args.ref, args.input, batch=args.batch, flags=args.flags)
+    print(json.dumps(metrics.report(res, args.ref, args.input, per_frame=args.per_frame)))
+    return 0
+
+
 def _avi(path):
     return str(path).lower().endswith(".avi")
 
@@ -727,6 +735,14 @@ def main(argv=None):
     p.add_argument("--per-frame", action="store_true")
     p.add_argument("--normalize", action="store_true", help="SI/TI on the 8-bit scale (/ 2^(bitdepth-8))")
     p.set_defaults(fn=cmd_siti)
+
+    p = sub.add_parser("metrics")
+    p.add_argument("--ref", required=True, help="the source clip (SRC)")
+    p.add_argument("--input", required=True, help="the distorted clip (AVPVS)")
+    p.add_argument("--batch", type=int, default=32)
+    p.add_argument("--flags", default="bicubic", help="scaler bringing the SRC to the input's size and format")
+    p.add_argument("--per-frame", action="store_true")
+    p.set_defaults(fn=cmd_metrics)
 
     args = ap.parse_args(argv)
     # GPU FFV1 applies to AVI files (the reference's AVPVS container); Y4M /

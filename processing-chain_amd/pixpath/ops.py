@@ -197,6 +197,36 @@ def siti(luma, bitdepth, prev=None, stream=None, normalize=False):
     return si, ti
 
 
+def metrics(ref, dist, ref_index=None, stream=None):
+    """Per-frame, per-plane SSE and SSIM of ``dist`` against ``ref`` (spec
+    PP-METRIC-1): two FrameBatches of one planar format and size, any pitches.
+    dist frame k is compared with ref frame ``ref_index[k]`` (None: frame k).
+    Returns device tensors (sse int64 [N, 3], ssim float64 [N, 3]); the SSIM of
+    a plane under 8 samples wide or high is NaN."""
+    if (ref.fmt.id, ref.w, ref.h) != (dist.fmt.id, dist.w, dist.h):
+        raise ValueError("ref and dist differ in format or size")
+    if ref.device != dist.device:
+        raise ValueError("ref and dist are on different devices")
+    n = dist.n
+    ri = None
+    if ref_index is not None:
+        ri = np.ascontiguousarray(ref_index, dtype=np.int32)
+        if ri.shape != (n,):
+            raise ValueError("ref_index needs one entry per dist frame")
+        if ri.size and ri.max() >= ref.n:
+            raise ValueError("ref index out of range")
+    elif ref.n < n:
+        raise ValueError("ref has fewer frames than dist")
+    ctx = context(dist.device.index)
+    sse = torch.empty((n, 3), dtype=torch.int64, device=dist.device)
+    ssim = torch.empty((n, 3), dtype=torch.float64, device=dist.device)
+    r, d = ref.frames_struct(), dist.frames_struct()
+    check(lib().pp_metrics(ctx.handle, dist.fmt.id, dist.w, dist.h, ctypes.byref(r), ctypes.byref(d),
+                           None if ri is None else ri.ctypes.data, n, ctypes.c_void_p(sse.data_ptr()),
+                           ctypes.c_void_p(ssim.data_ptr()), _stream(dist.planes[0], stream)))
+    return sse, ssim
+
+
 def spinner_upload(rgba_frames, f, device=None):
     """Upload an RGBA8 animation [n, h, w, 4] (host) for stall compositing."""
     a = np.ascontiguousarray(rgba_frames, dtype=np.uint8)
