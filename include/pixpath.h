@@ -116,6 +116,47 @@ int pp_scale_plan_path(const pp_scale_plan *plan);
  * luma staged columns, luma window rows, luma max new rows per chunk}.
  * Returns the number of values written. */
 int pp_scale_plan_stats(const pp_scale_plan *plan, int64_t *out, int n);
+/* Which compiled kernel instances pp_scale_execute launches for this plan.
+ * The strip, packed, chain and general-kernel launchers pick their kernel
+ * through the code that fills the key, so for those the report is the choice;
+ * the list of launches itself (unscaled converters, the two-launch chain)
+ * restates the executor.
+ * Works on host-only plans.  vec_src: every source plane pointer, linesize and
+ * frame stride is 16-B aligned; vec_dst: every destination plane's is 8-B
+ * aligned (4-B for 8-bit planar output).  One key of PP_SCALE_KEY_FIELDS
+ * int32 per launch, in launch order:
+ *   [0] family (PP_SCALE_FAM_*)
+ *   [1] source sample bytes (1, 2)      [2] output bits (8, 10)
+ *   [3] strip families: H window dwords (HW); general kernel: H-tap bucket (HT)
+ *   [4] strip families: V tap-pair bucket (VTM), else 0
+ *   [5] 1 = the DIRECT instance (8-bit source, HW 8, plain)
+ *   [6] 1 = 256-column strips (general kernel: the TW-256 variant)
+ *   [7] second-stage V tap pairs of a chain launch's fuse-2 planes, else 0
+ *   [8] 1 = every strip of the launch runs the clamped V pass (vector stores,
+ *       every plane width a multiple of 4), 0 = a per-lane strip exists
+ *   [9] 1 = the instance compiles the clamped V-pass copy at all
+ *   [10] output rows per chunk of the launch's first plane (0: no chunks)
+ *   [11] fewest chunks any plane of the launch walks in one segment (a chain
+ *        launch's second-stage planes: over their whole height); >= 2 means
+ *        every plane carries window rows from one chunk to the next
+ * A fused 4:2:2 chain with its own luma plan reports two keys (luma launch,
+ * chroma launch); a two-launch chain reports PP_SCALE_FAM_TWO_LAUNCH followed
+ * by the keys of its first and second stage; a packed plan off the strip path
+ * reports the general kernel and PP_SCALE_FAM_INTERLEAVE.
+ * Returns the number of keys (<= 8), or < 0 (PP_ERR_INVALID when `capacity`,
+ * in keys, is too small).  Added without raising PP_ABI_VERSION. */
+#define PP_SCALE_KEY_FIELDS 12
+#define PP_SCALE_FAM_PLAIN 0
+#define PP_SCALE_FAM_PACKED 1
+#define PP_SCALE_FAM_CHAIN 2
+#define PP_SCALE_FAM_CHAIN_LUMA 3
+#define PP_SCALE_FAM_CHAIN_CHROMA 4
+#define PP_SCALE_FAM_GENERAL 5
+#define PP_SCALE_FAM_COPY 6
+#define PP_SCALE_FAM_INTERLEAVE 7
+#define PP_SCALE_FAM_TWO_LAUNCH 8
+int pp_scale_plan_instances(const pp_scale_plan *plan, int vec_src, int vec_dst,
+                            int32_t *out, int capacity);
 /* The two-stage chain of create_avpvs_segment (lib/ffmpeg.py:1037-1048):
  * `scale=W:H:flags=...` into the overlay's yuv420p, then libavfilter's
  * auto-inserted yuv420p -> dst_fmt conversion at the same size (bicubic).

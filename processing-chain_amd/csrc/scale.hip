@@ -577,6 +577,145 @@ int scratch_batch(pp_scale_plan *P, int64_t ys, int64_t cs, int nframes, pp_fram
     return PP_OK;
 }
 
+// ---------------------------------------------------------------------------
+// Which compiled kernel a launch runs.  The strip, packed, chain and general
+// launchers below pick their kernel through these functions and
+// pp_scale_plan_instances reports what they return, so for those launches the
+// report is the choice.  Which launches a plan makes (plan_keys: unscaled
+// converters, the two-launch chain, the scratch batch's alignment) restates
+// execute_kind and has to be kept in step with it by hand.
+struct KernelKey {
+    int family;      // PP_SCALE_FAM_*
+    int sbytes;      // source sample bytes
+    int outb;        // output bits (a chain launch: the chain's target depth)
+    int win;         // strip families: HW; general kernel: HT
+    int vtm;         // strip families: V tap-pair bucket
+    int direct;      // strip_kernel's DIRECT instance
+    int tw256;       // 256-column strips
+    int vtp2;        // second-stage V tap pairs (fuse-2 planes of a chain launch)
+    int clamped;     // every strip of the launch takes the clamped V pass
+    int clamp_path;  // the instance compiles the clamped V-pass copy
+    int cho;         // output rows per chunk of the launch's first plane
+    int chunks;      // fewest chunks a plane of the launch walks per segment (fuse-2 planes: over their height)
+};
+
+// chunk geometry of a launch over `np` jobs, for the report only
+void key_chunks(KernelKey &k, const PlaneJob *const *jobs, int np) {
+    k.cho = jobs[0]->cho;
+    k.chunks = INT_MAX;
+    for (int i = 0; i < np; ++i) {
+        const PlaneJob &J = *jobs[i];
+        const int rows = J.fuse == 2 ? J.dh : std::min(J.dh, J.seg_h);
+        k.chunks = std::min(k.chunks, (rows + J.cho - 1) / J.cho);
+    }
+}
+
+KernelFn kernel_for(const KernelKey &k) {
+    using namespace pp;
+    const bool u8 = k.sbytes == 1;
+    switch (k.family) {
+    case PP_SCALE_FAM_PLAIN:
+        return u8 ? pick_strip_u8(k.outb, k.win, k.vtm, k.tw256 ? 256 : 512)
+                  : pick_strip_u16(k.outb, k.win, k.vtm, k.tw256 ? 256 : 512);
+    case PP_SCALE_FAM_PACKED: return u8 ? pick_strip_packed_u8(k.win, k.vtm) : pick_strip_packed_u16(k.win, k.vtm);
+    case PP_SCALE_FAM_CHAIN:
+        return u8 ? pick_strip_chain_u8(k.outb, k.win, k.vtm) : pick_strip_chain_u16(k.outb, k.win, k.vtm);
+    case PP_SCALE_FAM_CHAIN_LUMA: return u8 ? pick_strip_luma_u8(k.win, k.vtm) : pick_strip_luma_u16(k.win, k.vtm);
+    case PP_SCALE_FAM_CHAIN_CHROMA: return u8 ? pick_strip_chroma_u8(k.win, k.vtm) : pick_strip_chroma_u16(k.win, k.vtm);
+    case PP_SCALE_FAM_GENERAL:
+        if (u8) return k.outb == 8 ? pick_ht<uint8_t, 8>(k.win, k.tw256) : pick_ht<uint8_t, 10>(k.win, k.tw256);
+        return k.outb == 8 ? pick_ht<uint16_t, 8>(k.win, k.tw256) : pick_ht<uint16_t, 10>(k.win, k.tw256);
+    default: return nullptr;
+    }
+}
+
+// a strip launch over `np` jobs is clamped when rows take vector stores and
+// every plane's width is a multiple of 4 (strip.hpp: `clamp`, per strip)
+bool jobs_clamped(const PlaneJob *const *jobs, int np, bool vdst) {
+    bool c = vdst;
+    for (int i = 0; i < np; ++i) c = c && (jobs[i]->dw & 3) == 0;
+    return c;
+}
+
+// launch_generic: the strip kernel for strip plans on vector-loadable
+// sources, else the general kernel's H-tap bucket
+// (an 8-bit HW-8 plan takes the strip path only with its DIRECT tiling:
+// that instance stages no rows)
+KernelKey generic_key(const ScaleLayout &L, int out_depth, bool vsrc, bool vdst) {
+    using namespace pp;
+    KernelKey k{};
+    k.sbytes = L.si.depth == 8 ? 1 : 2;
+    k.outb = out_depth == 8 ? 8 : 10;
+    if (L.fast_hw && vsrc && (L.direct || !(L.si.depth == 8 && L.fast_hw == 8))) {
+        k.family = PP_SCALE_FAM_PLAIN;
+        k.win = L.fast_hw;
+        k.vtm = strip_vtm_bucket(std::max(L.fjob[0].vtp, L.fjob[1].vtp));
+        k.direct = L.si.depth == 8 && L.fast_hw == 8;
+        k.tw256 = L.fast_tw == 256;
+        k.clamp_path = strip_clamp_rule(k.sbytes, k.outb, k.win, k.vtm, 0);
+        const PlaneJob *jobs[3] = {&L.fjob[0], &L.fjob[1], &L.fjob[2]};
+        k.clamped = k.clamp_path && jobs_clamped(jobs, 3, vdst);
+        key_chunks(k, jobs, 3);
+    } else {
+        k.family = PP_SCALE_FAM_GENERAL;
+        k.win = L.ht;
+        k.tw256 = L.job[0].tw == kTileW && L.job[1].tw == kTileW && L.job[2].tw == kTileW;
+        const PlaneJob *jobs[3] = {&L.job[0], &L.job[1], &L.job[2]};
+        key_chunks(k, jobs, 3);
+    }
+    return k;
+}
+
+// launch_packed (never clamped: per-lane byte stores into the packed row)
+KernelKey packed_key(const ScaleLayout &L) {
+    KernelKey k{};
+    k.family = PP_SCALE_FAM_PACKED;
+    k.sbytes = L.si.depth == 8 ? 1 : 2;
+    k.outb = 8;
+    k.win = L.fast_hw;
+    k.vtm = pp::strip_vtm_bucket(std::max(L.fjob[0].vtp, L.fjob[1].vtp));
+    k.tw256 = 1;
+    const PlaneJob *jobs[3] = {&L.fjob[0], &L.fjob[1], &L.fjob[2]};
+    key_chunks(k, jobs, 3);
+    return k;
+}
+
+// launch_chain_planes over `np` jobs with window `hw`
+KernelKey chain_key(const ScaleLayout &L, bool has_luma, const PlaneJob *const *jobs, int np, int hw, bool luma_only,
+                    bool vdst) {
+    using namespace pp;
+    KernelKey k{};
+    k.sbytes = L.si.depth == 8 ? 1 : 2;
+    k.outb = L.chain_out;
+    k.win = hw;
+    k.tw256 = 1;
+    int vtp = 1;
+    for (int i = 0; i < np; ++i) {
+        vtp = std::max(vtp, jobs[i]->vtp);
+        if (jobs[i]->fuse == 2) k.vtp2 = jobs[i]->vtp2;
+    }
+    k.vtm = strip_vtm_bucket(vtp);
+    key_chunks(k, jobs, np);
+    // the luma launch of a 10-bit chain (fuse 1 into 10 bits) takes its own
+    // instance without the ring2 / second-stage code (FUSE 9)
+    // (clamped plans only: every plane's width a multiple of 4 with vector
+    // stores, so those instances compile the clamped V pass alone)
+    const bool clamped = jobs_clamped(jobs, np, vdst);
+    const bool l9 = clamped && luma_only && L.chain_out == 10 && jobs[0]->fuse == 1 && !PP_KNOB("PIXPATH_CHAIN_NO_LUMA9");
+    // ... and the chroma launch (every plane fuse 2) FUSE 11
+    bool c11 = clamped && !luma_only && has_luma && L.chain_out == 10 && !PP_KNOB("PIXPATH_CHAIN_NO_CHROMA11");
+    for (int i = 0; i < np; ++i) c11 = c11 && jobs[i]->fuse == 2;
+    if (l9 || c11) {  // (FUSE 9 / 11 exist for narrow windows only)
+        k.family = l9 ? PP_SCALE_FAM_CHAIN_LUMA : PP_SCALE_FAM_CHAIN_CHROMA;
+        k.clamp_path = k.clamped = 1;
+        if (kernel_for(k)) return k;
+    }
+    k.family = PP_SCALE_FAM_CHAIN;
+    k.clamp_path = strip_clamp_rule(k.sbytes, 8, k.win, k.vtm, L.chain_out);
+    k.clamped = k.clamp_path && clamped;
+    return k;
+}
+
 int launch_generic(pp_scale_plan *P, const pp_frames *src, const pp_frames *dst, int nframes, hipStream_t st,
                    int out_depth, bool allow_dither) {
     using namespace pp;
@@ -594,26 +733,17 @@ int launch_generic(pp_scale_plan *P, const pp_frames *src, const pp_frames *dst,
     if (const char *e = PP_KNOB("PIXPATH_SCALE_DEBUG")) a.debug = atoi(e);
     for (int p = 0; p < 3; ++p)
         a.vec_dst &= aligned(a.dst[p], a.dls[p], nframes > 1 ? a.dfs[p] : 0, out_depth == 8 ? 4 : 8);
-    const bool tw256 = L.job[0].tw == kTileW && L.job[1].tw == kTileW && L.job[2].tw == kTileW;
-    KernelFn k;
     size_t lds = L.lds_bytes;
     int threads = kThreads;
     a.tiles = L.job[2].tile_base + L.job[2].tiles_x * L.job[2].tiles_y;
-    // (an 8-bit HW-8 plan takes the strip path only with its DIRECT tiling:
-    // that instance stages no rows)
-    if (L.fast_hw && a.vec_src && (L.direct || !(L.si.depth == 8 && L.fast_hw == 8))) {
+    const KernelKey key = generic_key(L, out_depth, a.vec_src != 0, a.vec_dst != 0);
+    if (key.family == PP_SCALE_FAM_PLAIN) {
         for (int p = 0; p < 3; ++p) a.pl[p] = L.fjob[p];
         lds = L.fast_lds;
         a.tiles = L.fast_tiles;
         threads = L.fast_tw;
-        const int vtm = strip_vtm_bucket(std::max(L.fjob[0].vtp, L.fjob[1].vtp));
-        k = L.si.depth == 8 ? pick_strip_u8(out_depth, L.fast_hw, vtm, L.fast_tw)
-                            : pick_strip_u16(out_depth, L.fast_hw, vtm, L.fast_tw);
-    } else if (L.si.depth == 8) {
-        k = out_depth == 8 ? pick_ht<uint8_t, 8>(L.ht, tw256) : pick_ht<uint8_t, 10>(L.ht, tw256);
-    } else {
-        k = out_depth == 8 ? pick_ht<uint16_t, 8>(L.ht, tw256) : pick_ht<uint16_t, 10>(L.ht, tw256);
     }
+    KernelFn k = kernel_for(key);
     if (!k) PP_FAIL(PP_ERR_UNSUPPORTED, "no kernel for %d taps", L.ht);
     return launch_frames(k, a, threads, lds, nframes, st);
 }
@@ -636,8 +766,7 @@ int launch_packed(pp_scale_plan *P, const pp_frames *src, const pp_frames *dst, 
     a.dither = 0;  // yuv2packedX rounds with 1 << 18, never dithers
     a.vec_src = 1;
     a.vec_dst = 0;
-    const int vtm = strip_vtm_bucket(std::max(L.fjob[0].vtp, L.fjob[1].vtp));
-    KernelFn k = L.si.depth == 8 ? pick_strip_packed_u8(L.fast_hw, vtm) : pick_strip_packed_u16(L.fast_hw, vtm);
+    KernelFn k = kernel_for(packed_key(L));
     if (!k) PP_FAIL(PP_ERR_UNSUPPORTED, "no packed kernel for window %d", L.fast_hw);
     a.tiles = L.fast_tiles;
     return launch_frames(k, a, kThreads, L.fast_lds, nframes, st);
@@ -653,12 +782,10 @@ int launch_chain_planes(pp_scale_plan *P, const PlaneJob *const *jobs, const int
     const ScaleLayout &L = *P->lay;
     ScaleArgs a{};
     a.nplanes = np;
-    int vtp = 1;
     for (int i = 0; i < np; ++i) {
         a.pl[i] = *jobs[i];
         a.pl[i].tile_base = a.tiles;
         a.tiles += a.pl[i].tiles_x * a.pl[i].tiles_y;
-        vtp = std::max(vtp, a.pl[i].vtp);
         set_plane(a, i, src, pl[i], dst, pl[i]);
     }
     a.hshift = L.si.depth == 8 ? 7 : L.si.depth - 1;
@@ -668,71 +795,126 @@ int launch_chain_planes(pp_scale_plan *P, const PlaneJob *const *jobs, const int
     if (const char *e = PP_KNOB("PIXPATH_SCALE_DEBUG")) a.debug = atoi(e);
     for (int i = 0; i < np; ++i)
         a.vec_dst &= aligned(a.dst[i], a.dls[i], nframes > 1 ? a.dfs[i] : 0, L.chain_out == 8 ? 4 : 8);
-    const int vtm = strip_vtm_bucket(vtp);
-    // the luma launch of a 10-bit chain (fuse 1 into 10 bits) takes its own
-    // instance without the ring2 / second-stage code (FUSE 9)
-    // (clamped plans only: every plane's width a multiple of 4 with vector
-    // stores, so those instances compile the clamped V pass alone)
-    bool clamped = a.vec_dst != 0;
-    for (int i = 0; i < np; ++i) clamped = clamped && (jobs[i]->dw & 3) == 0;
-    const bool l9 = clamped && luma_only && L.chain_out == 10 && jobs[0]->fuse == 1 && !PP_KNOB("PIXPATH_CHAIN_NO_LUMA9");
-    // ... and the chroma launch (every plane fuse 2) FUSE 11
-    bool c11 = clamped && !luma_only && P->luma && L.chain_out == 10 && !PP_KNOB("PIXPATH_CHAIN_NO_CHROMA11");
-    for (int i = 0; i < np; ++i) c11 = c11 && jobs[i]->fuse == 2;
-    const bool u8 = L.si.depth == 8;
-    KernelFn k = l9 ? (u8 ? pick_strip_luma_u8(hw, vtm) : pick_strip_luma_u16(hw, vtm))
-                    : c11 ? (u8 ? pick_strip_chroma_u8(hw, vtm) : pick_strip_chroma_u16(hw, vtm)) : nullptr;
-    if (!k)  // (FUSE 9 / 11 exist for narrow windows only)
-        k = u8 ? pick_strip_chain_u8(L.chain_out, hw, vtm) : pick_strip_chain_u16(L.chain_out, hw, vtm);
+    KernelFn k = kernel_for(chain_key(L, P->luma != nullptr, jobs, np, hw, luma_only, a.vec_dst != 0));
     if (!k) PP_FAIL(PP_ERR_UNSUPPORTED, "no chain kernel for window %d", hw);
     return launch_frames(k, a, kThreads, lds, nframes, st);
 }
 
-// CHAIN, fused: one launch over all planes, or (P->luma) the luma launch of
-// the plain first-stage plan, then the chroma planes' chain launch
-int launch_chain(pp_scale_plan *P, const pp_frames *src, const pp_frames *dst, int nframes, hipStream_t st) {
-    using namespace pp;
+// The launches of a fused CHAIN plan: one over all planes, or (P->luma) the
+// luma launch of the plain first-stage plan, then the chroma planes' chain launch
+struct ChainLaunch {
+    const PlaneJob *jobs[3];
+    int pl[3];
+    int np, hw;
+    size_t lds;
+    bool luma_only;
+};
+
+int chain_launches(const pp_scale_plan *P, ChainLaunch out[2]) {
     const ScaleLayout &L = *P->lay;
     if (P->luma && P->luma->lay->fast_hw == L.fast_hw && PP_KNOB("PIXPATH_CHAIN_COMBINED")) {
         // measurement: the luma plan's job (32-row chunks) and the chroma
         // chain jobs in ONE launch, LDS the larger of the two layouts
-        const PlaneJob *jobs[3] = {&P->luma->lay->fjob[0], &L.fjob[1], &L.fjob[2]};
-        const int pl[3] = {0, 1, 2};
-        return launch_chain_planes(P, jobs, pl, 3, L.fast_hw, std::max(P->luma->lay->fast_lds_plane[0], L.chain_lds),
-                                   src, dst, nframes, st);
+        out[0] = ChainLaunch{{&P->luma->lay->fjob[0], &L.fjob[1], &L.fjob[2]}, {0, 1, 2}, 3, L.fast_hw,
+                             std::max(P->luma->lay->fast_lds_plane[0], L.chain_lds), false};
+        return 1;
     }
     if (P->luma) {
         const ScaleLayout &LL = *P->luma->lay;
-        // PIXPATH_CHAIN_OVERLAP (measurement build): the luma launch on a side
-        // stream, concurrent with the chroma launch (fork / join events on `st`)
-        const bool overlap = PP_KNOB("PIXPATH_CHAIN_OVERLAP") != nullptr;
-        hipStream_t ls = st;
-        if (overlap) {
-            if (!P->side) {
-                PP_HIP(hipStreamCreateWithFlags(&P->side, hipStreamNonBlocking));
-                PP_HIP(hipEventCreateWithFlags(&P->fork, hipEventDisableTiming));
-                PP_HIP(hipEventCreateWithFlags(&P->join, hipEventDisableTiming));
-            }
-            PP_HIP(hipEventRecord(P->fork, st));
-            PP_HIP(hipStreamWaitEvent(P->side, P->fork, 0));
-            ls = P->side;
-        }
-        const PlaneJob *lj[1] = {&LL.fjob[0]};
-        const int lpl[1] = {0};
-        if (int rc = launch_chain_planes(P, lj, lpl, 1, LL.fast_hw, LL.fast_lds_plane[0], src, dst, nframes, ls, true))
-            return rc;
-        const PlaneJob *cj[2] = {&L.fjob[1], &L.fjob[2]};
-        const int cpl[2] = {1, 2};
-        const int rc = launch_chain_planes(P, cj, cpl, 2, L.fast_hw, L.chain_lds, src, dst, nframes, st);
-        if (overlap) {
-            PP_HIP(hipEventRecord(P->join, P->side));
-            PP_HIP(hipStreamWaitEvent(st, P->join, 0));
-        }
-        return rc;
+        out[0] = ChainLaunch{{&LL.fjob[0], nullptr, nullptr}, {0, 0, 0}, 1, LL.fast_hw, LL.fast_lds_plane[0], true};
+        out[1] = ChainLaunch{{&L.fjob[1], &L.fjob[2], nullptr}, {1, 2, 0}, 2, L.fast_hw, L.chain_lds, false};
+        return 2;
     }
-    const PlaneJob *jobs[3] = {&L.fjob[0], &L.fjob[1], &L.fjob[2]};
-    const int pl[3] = {0, 1, 2};
-    return launch_chain_planes(P, jobs, pl, 3, L.fast_hw, L.chain_lds, src, dst, nframes, st);
+    out[0] = ChainLaunch{{&L.fjob[0], &L.fjob[1], &L.fjob[2]}, {0, 1, 2}, 3, L.fast_hw, L.chain_lds, false};
+    return 1;
+}
+
+int launch_chain(pp_scale_plan *P, const pp_frames *src, const pp_frames *dst, int nframes, hipStream_t st) {
+    using namespace pp;
+    ChainLaunch cl[2];
+    const int n = chain_launches(P, cl);
+    auto go = [&](const ChainLaunch &c, hipStream_t s) {
+        return launch_chain_planes(P, c.jobs, c.pl, c.np, c.hw, c.lds, src, dst, nframes, s, c.luma_only);
+    };
+    if (n == 1) return go(cl[0], st);
+    // PIXPATH_CHAIN_OVERLAP (measurement build): the luma launch on a side
+    // stream, concurrent with the chroma launch (fork / join events on `st`)
+    const bool overlap = PP_KNOB("PIXPATH_CHAIN_OVERLAP") != nullptr;
+    hipStream_t ls = st;
+    if (overlap) {
+        if (!P->side) {
+            PP_HIP(hipStreamCreateWithFlags(&P->side, hipStreamNonBlocking));
+            PP_HIP(hipEventCreateWithFlags(&P->fork, hipEventDisableTiming));
+            PP_HIP(hipEventCreateWithFlags(&P->join, hipEventDisableTiming));
+        }
+        PP_HIP(hipEventRecord(P->fork, st));
+        PP_HIP(hipStreamWaitEvent(P->side, P->fork, 0));
+        ls = P->side;
+    }
+    if (int rc = go(cl[0], ls)) return rc;
+    const int rc = go(cl[1], st);
+    if (overlap) {
+        PP_HIP(hipEventRecord(P->join, P->side));
+        PP_HIP(hipStreamWaitEvent(st, P->join, 0));
+    }
+    return rc;
+}
+
+// which path a CHAIN / GENERIC_UYVY plan executes for a source alignment
+bool chain_runs_fused(const ScaleLayout &L, bool vsrc) { return L.chain_fused && vsrc; }
+bool packed_runs_strip(const ScaleLayout &L, bool vsrc) { return L.fast_hw && vsrc; }
+// the plan-owned scratch batch (scratch_batch) has dense rows (linesize = plane
+// width) in a fresh allocation: its alignment as a destination / source.
+// Exact for the chain's scratch (frame strides rounded to 16 B); the packed
+// path's strides are unrounded, so with more than one frame its general-kernel
+// launch may store per lane where this says vector -- the same kernel either way.
+bool scratch_aligned(const ScaleLayout &L, int a) { return L.dw % a == 0 && L.cdw % a == 0; }
+
+// the keys of every launch execute_kind(P, kind, ...) makes
+void plan_keys(const pp_scale_plan *P, ScaleLayout::Kind kind, bool vsrc, bool vdst, std::vector<KernelKey> &out) {
+    const ScaleLayout &L = *P->lay;
+    KernelKey k{};
+    k.sbytes = L.si.depth == 8 ? 1 : 2;
+    k.outb = L.di.depth == 8 ? 8 : 10;
+    switch (kind) {
+    case ScaleLayout::COPY:
+        k.family = PP_SCALE_FAM_COPY;
+        out.push_back(k);
+        return;
+    case ScaleLayout::INTERLEAVE:
+        k.family = PP_SCALE_FAM_INTERLEAVE;
+        out.push_back(k);
+        return;
+    case ScaleLayout::GENERIC:
+        out.push_back(generic_key(L, L.di.depth, vsrc, vdst));
+        return;
+    case ScaleLayout::CHAIN: {
+        if (chain_runs_fused(L, vsrc)) {
+            ChainLaunch cl[2];
+            const int n = chain_launches(P, cl);
+            for (int i = 0; i < n; ++i)
+                out.push_back(chain_key(L, P->luma != nullptr, cl[i].jobs, cl[i].np, cl[i].hw, cl[i].luma_only, vdst));
+            return;
+        }
+        k.family = PP_SCALE_FAM_TWO_LAUNCH;
+        k.outb = L.chain_out;
+        out.push_back(k);
+        plan_keys(P, L.first_kind, vsrc, scratch_aligned(L, 4), out);
+        plan_keys(P->stage2, P->stage2->lay->kind, scratch_aligned(L, 16), vdst, out);
+        return;
+    }
+    case ScaleLayout::GENERIC_UYVY:
+        if (packed_runs_strip(L, vsrc)) {
+            out.push_back(packed_key(L));
+            return;
+        }
+        out.push_back(generic_key(L, 8, vsrc, scratch_aligned(L, 4)));
+        k.family = PP_SCALE_FAM_INTERLEAVE;
+        k.sbytes = 1;
+        k.outb = 8;
+        out.push_back(k);
+        return;
+    }
 }
 
 void launch_interleave(const pp_frames *src, const pp_frames *dst, int w, int h, int nframes, hipStream_t st) {
@@ -744,6 +926,20 @@ void launch_interleave(const pp_frames *src, const pp_frames *dst, int w, int h,
 }
 
 }  // namespace
+
+extern "C" int pp_scale_plan_instances(const pp_scale_plan *P, int vsrc, int vdst, int32_t *out, int capacity) {
+    if (!P || !out || capacity < 0) PP_FAIL(PP_ERR_INVALID, "null argument");
+    std::vector<KernelKey> keys;
+    plan_keys(P, P->lay->kind, vsrc != 0, vdst != 0, keys);
+    if ((int)keys.size() > capacity) PP_FAIL(PP_ERR_INVALID, "capacity %d < %d keys", capacity, (int)keys.size());
+    for (size_t i = 0; i < keys.size(); ++i) {
+        const KernelKey &k = keys[i];
+        const int32_t v[PP_SCALE_KEY_FIELDS] = {k.family, k.sbytes, k.outb,    k.win,        k.vtm, k.direct,
+                                                k.tw256,  k.vtp2,   k.clamped, k.clamp_path, k.cho, k.chunks};
+        std::memcpy(out + i * PP_SCALE_KEY_FIELDS, v, sizeof(v));
+    }
+    return (int)keys.size();
+}
 
 static int execute_kind(pp_scale_plan *P, ScaleLayout::Kind kind, const pp_frames *src, const pp_frames *dst,
                         int nframes, void *stream) {
@@ -771,7 +967,7 @@ static int execute_kind(pp_scale_plan *P, ScaleLayout::Kind kind, const pp_frame
     case ScaleLayout::GENERIC:
         return launch_generic(P, src, dst, nframes, st, L.di.depth, true);
     case ScaleLayout::CHAIN: {
-        if (L.chain_fused && vec_src(src, nframes)) return launch_chain(P, src, dst, nframes, st);
+        if (chain_runs_fused(L, vec_src(src, nframes))) return launch_chain(P, src, dst, nframes, st);
         // two launches through a yuv420p scratch batch
         pp_frames tmp;
         if (int rc = scratch_batch(P, (yb + 15) & ~int64_t(15), (cb + 15) & ~int64_t(15), nframes, &tmp)) return rc;
@@ -779,7 +975,7 @@ static int execute_kind(pp_scale_plan *P, ScaleLayout::Kind kind, const pp_frame
         return pp_scale_execute(P->stage2, &tmp, dst, nframes, stream);
     }
     case ScaleLayout::GENERIC_UYVY: {
-        if (L.fast_hw && vec_src(src, nframes)) return launch_packed(P, src, dst, nframes, st);
+        if (packed_runs_strip(L, vec_src(src, nframes))) return launch_packed(P, src, dst, nframes, st);
         // yuv2packedX: planar 8-bit 4:2:2 (flat rounding: 1 << 18, never dithers) then interleave
         pp_frames tmp;
         if (int rc = scratch_batch(P, yb, cb, nframes, &tmp)) return rc;

@@ -185,5 +185,11 @@ KernelFn pick_strip_chroma_u8(int hw, int vtm);
 KernelFn pick_strip_packed_u16(int hw, int vtm);
 KernelFn pick_strip_packed_u8(int hw, int vtm);
 int strip_vtm_bucket(int vtp);
+// strip.hpp's strip_clamp_path() as a function of the instance's parameters
+// (SB source sample bytes; OUTB the kernel's first-stage output bits), so the
+// host can report it (pp_scale_plan_instances)
+constexpr bool strip_clamp_rule(int sb, int outb, int hw, int vtm, int fuse) {
+    return !(fuse >= 8 && hw >= 10) && !(sb == 1 && outb == 8 && hw == 4 && (fuse >= 8 || vtm >= 5));
+}
 
 }  // namespace pp

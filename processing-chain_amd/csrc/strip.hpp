@@ -166,7 +166,7 @@ constexpr int strip_fused_min_waves() {
 // windows, chain plans with 10+ dword windows spilled 1-5 VGPRs with it).
 template <typename ST, int OUTB, int HW, int VTM, int FUSE>
 constexpr bool strip_clamp_path() {
-    return !(FUSE >= 8 && HW >= 10) && !(sizeof(ST) == 1 && OUTB == 8 && HW == 4 && (FUSE >= 8 || VTM >= 5));
+    return strip_clamp_rule((int)sizeof(ST), OUTB, HW, VTM, FUSE);
 }
 
 template <typename ST, int OUTB, int HW, int VTM, int FUSE = 0, int TW = 256>

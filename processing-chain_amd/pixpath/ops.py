@@ -4,6 +4,7 @@ Every function enqueues on the current torch stream of the frames' device
 (or an explicit ``stream``) and returns without synchronising.  There is no
 CPU fallback: a missing libpixpath.so raises ``NativeMissing``.
 """
+import collections
 import ctypes
 from fractions import Fraction
 
@@ -17,6 +18,11 @@ from .frames import FrameBatch
 FLAGS = {"bilinear": 0x2, "bicubic": 0x4, "lanczos": 0x200}
 PARAM_DEFAULT = 123456.0
 PLAN_GENERIC = 0x10000000  # PP_PLAN_GENERIC (ABI v5)
+
+# PP_SCALE_FAM_* (pp_scale_plan_instances), by value
+FAMILIES = ("plain", "packed", "chain", "chain-luma", "chain-chroma", "general", "copy", "interleave", "two-launch")
+InstanceKey = collections.namedtuple(
+    "InstanceKey", "family sbytes outb win vtm direct tw256 vtp2 clamped clamp_path cho chunks")
 
 _contexts = {}
 
@@ -64,22 +70,24 @@ class Scaler:
     """
 
     def __init__(self, src_fmt, sw, sh, dst_fmt, dw, dh, flags="bicubic", param0=None, param1=None,
-                 device=None, chain=False, generic=False):
+                 device=None, chain=False, generic=False, host_only=False):
         """chain=True: create_avpvs_segment's two stages (scale into the overlay's
         yuv420p, then yuv420p -> dst_fmt bicubic at the same size) as one plan
         (pp_scale_chain_plan_create): one launch when kernel_path > 0.
         generic=True: the general scale_kernel even where the strip kernel
-        applies (PP_PLAN_GENERIC; both are bit-exact, tests run both)."""
+        applies (PP_PLAN_GENERIC; both are bit-exact, tests run both).
+        host_only=True: a plan without a context (no GPU needed): introspection
+        only (kernel_path, stats, filter, instance_keys), it cannot execute."""
         self.src_fmt, self.dst_fmt = formats.fmt(src_fmt), formats.fmt(dst_fmt)
         self.sw, self.sh, self.dw, self.dh = int(sw), int(sh), int(dw), int(dh)
-        self.ctx = context(device)
+        self.ctx = None if host_only else context(device)
         fl = FLAGS[flags] if isinstance(flags, str) else int(flags)
         if generic:
             fl |= PLAN_GENERIC
         h = ctypes.c_void_p()
         create = lib().pp_scale_chain_plan_create if chain else lib().pp_scale_plan_create
         check(create(
-            self.ctx.handle, self.src_fmt.id, self.sw, self.sh, self.dst_fmt.id, self.dw, self.dh, fl,
+            self.ctx.handle if self.ctx else None, self.src_fmt.id, self.sw, self.sh, self.dst_fmt.id, self.dw, self.dh, fl,
             PARAM_DEFAULT if param0 is None else float(param0),
             PARAM_DEFAULT if param1 is None else float(param1), ctypes.byref(h)))
         self.handle = h
@@ -106,6 +114,23 @@ class Scaler:
         n = check(lib().pp_scale_plan_stats(self.handle, v.ctypes.data, len(keys)))
         return dict(zip(keys[:n], (int(x) for x in v[:n])))
 
+    @property
+    def instance_keys(self):
+        """instance_keys_for() aligned sources and destinations."""
+        return self.instance_keys_for()
+
+    def instance_keys_for(self, vec_src=True, vec_dst=True):
+        """The compiled kernel instance of every launch this plan makes
+        (pp_scale_plan_instances), as InstanceKey tuples in launch order, for
+        16-B aligned source planes (vec_src) and 8-B aligned destination rows
+        (vec_dst)."""
+        cap, nf = 8, len(InstanceKey._fields)
+        v = np.zeros(cap * nf, dtype=np.int32)
+        n = check(lib().pp_scale_plan_instances(self.handle, int(bool(vec_src)), int(bool(vec_dst)),
+                                                v.ctypes.data, cap))
+        rows = v[: n * nf].reshape(n, nf).tolist()
+        return [InstanceKey(FAMILIES[r[0]], *r[1:]) for r in rows]
+
     def filter(self, which):
         """FFmpeg-layout filter (coef [n, size] int16, pos [n] int32) or None (unscaled path)."""
         n = [self.dw, -((-self.dw) >> (self.dst_fmt.hsub)), self.dh,
@@ -119,6 +144,8 @@ class Scaler:
         return coef[: n * size].reshape(n, size).copy(), pos
 
     def __call__(self, src, dst=None, stream=None):
+        if self.ctx is None:
+            raise ValueError("a host-only plan cannot execute")
         if (src.fmt.id, src.w, src.h) != (self.src_fmt.id, self.sw, self.sh):
             raise ValueError("source batch does not match the plan")
         if dst is None:
