@@ -185,7 +185,8 @@ int pp_pad_execute(pp_ctx *ctx, int fmt, int src_w, int src_h,
 /* ---- CPVS packers ------------------------------------------------------
  * `-c:v v210 -pix_fmt yuv422p10le` (lib/test_config.py:208-215 via
  * lib/ffmpeg.py:1198): pack yuv422p10le into v210 (libavcodec/v210enc.c);
- * dst plane 0 with linesize >= pp_v210_linesize(w). */
+ * dst plane 0 with linesize >= pp_v210_linesize(w).  An odd w is
+ * PP_ERR_INVALID, as in FFmpeg ("v210 needs even width"). */
 int pp_v210_pack(pp_ctx *ctx, int w, int h, const pp_frames *src,
                  const pp_frames *dst, int nframes, void *stream);
 
@@ -194,7 +195,8 @@ int pp_v210_pack(pp_ctx *ctx, int w, int h, const pp_frames *src,
  * yuv420p/yuv422p for out_fmt PP_FMT_UYVY422, yuv420p10le/yuv422p10le for
  * PP_FMT_V210); canvas W x H with the input at (x, y) (-1 = centred, rounded
  * to the chroma grid); dst plane 0, 16-B aligned.  Bit-identical to pad ->
- * swscale (bicubic) -> packer. */
+ * swscale (bicubic) -> packer.  An odd W is PP_ERR_INVALID for both packings
+ * (uyvy422 pairs pixels; FFmpeg's v210 encoder refuses odd widths). */
 int pp_cpvs_execute(pp_ctx *ctx, int src_fmt, int w, int h, const pp_frames *src,
                     int W, int H, int x, int y, int out_fmt,
                     const pp_frames *dst, int nframes, void *stream);
@@ -211,6 +213,92 @@ int pp_spinner_upload(pp_ctx *ctx, int fmt, const uint8_t *rgba, int n,
 int pp_stall_compose(pp_ctx *ctx, int fmt, int w, int h, const pp_frames *src,
                      const int32_t *src_index, const int32_t *spinner_index,
                      const pp_frames *dst, int nframes, void *stream);
+
+/* ---- which code paths a pad / CPVS / v210 / stall launch takes ------------
+ * Host only: no GPU, no context, nothing is read through the data pointers.
+ * The pad and stall row kernels and the fused CPVS kernel choose a path per
+ * launch, row, 16-B chunk and chroma group (vector or sample-by-sample loads
+ * and stores, image edges, pad rows, v210 tails, spinner overlap, frame
+ * tiles ...).  The walker below runs the kernels' own predicates
+ * (csrc/pack_plan.hpp) over every row, chunk and group of the launch the
+ * query describes and reports the arms taken, so a test table can show that
+ * it reaches every one.  Bit numbers of the mask: */
+enum pp_pack_arm {
+    /* fused CPVS kernel, per instance (8 / 10 bit x 4:2:0 / 4:2:2) */
+    PP_ARM_CPVS_ROW_LIVE = 0,       /* canvas row inside the AVPVS */
+    PP_ARM_CPVS_ROW_PAD,            /* canvas row above / below it */
+    PP_ARM_CPVS_STAGE_VEC_ONE,      /* 16-B staging, one pass of 512 pieces */
+    PP_ARM_CPVS_STAGE_VEC_MULTI,    /* 16-B staging, two or more passes */
+    PP_ARM_CPVS_STAGE_SAMPLES,      /* unaligned rows: sample by sample */
+    PP_ARM_CPVS_GROUP_VEC,          /* 4:2:0 chroma group: vector loads */
+    PP_ARM_CPVS_GROUP_SAMPLES,      /* 4:2:0 chroma group: by samples */
+    PP_ARM_CPVS_GROUP_CLAMPED,      /* ragged last group: min(x, cw - 1) */
+    PP_ARM_CPVS_GROUP_VEC_RAGGED,   /* aligned rows, group past the padded row: unreachable (pack_plan.hpp) */
+    PP_ARM_CPVS_TAP_ABOVE,          /* vertical tap row above the image: black */
+    PP_ARM_CPVS_TAP_BELOW,          /* ... below it */
+    PP_ARM_CPVS_GROUPS_GT64,        /* more chroma groups than lanes */
+    PP_ARM_CPVS_C8_FAST,            /* uyvy422 chunk: 3 LDS words + v_perm */
+    PP_ARM_CPVS_C8_OFFGRID,         /* chunk inside the AVPVS, pad offset off the 8-px grid: by samples */
+    PP_ARM_CPVS_C8_SLOW_FULL,       /* other uyvy422 chunk by samples, 16-B store */
+    PP_ARM_CPVS_C8_SLOW_TAIL,       /* uyvy422 last chunk, byte stores */
+    PP_ARM_CPVS_V210_FULL,          /* v210 chunk of 6 pixels */
+    PP_ARM_CPVS_V210_TAIL2,         /* v210 tail, W % 6 == 2 */
+    PP_ARM_CPVS_V210_TAIL4,         /* v210 tail, W % 6 == 4 */
+    PP_ARM_CPVS_V210_ZERO,          /* zero fill up to the line size */
+    PP_ARM_CPVS_CHUNKS_GT64,        /* more output chunks than lanes */
+    /* pad and stall row kernels, per sample size */
+    PP_ARM_ROW_SRC_VEC,             /* source chunk: one 16-B load */
+    PP_ARM_ROW_SRC_EDGE,            /* vector mode, chunk across an image edge: by samples */
+    PP_ARM_ROW_SRC_OUTSIDE,         /* live row, chunk wholly in the pad columns (pad only) */
+    PP_ARM_ROW_SRC_SCALAR,          /* unaligned source or shift: by samples throughout */
+    PP_ARM_ROW_SRC_NULL,            /* no source row: black */
+    PP_ARM_ROW_DST_VEC,             /* 16-B store */
+    PP_ARM_ROW_DST_TAIL,            /* aligned destination, ragged last chunk */
+    PP_ARM_ROW_DST_SCALAR,          /* unaligned destination: by samples throughout */
+    PP_ARM_ROW_CHUNKS_GT256,        /* second trip of the chunk loop */
+    PP_ARM_ROW_420,
+    PP_ARM_ROW_422,
+    PP_ARM_ROW_444,
+    /* stall only */
+    PP_ARM_STALL_TILE_FULL,         /* tile of G frames */
+    PP_ARM_STALL_TILE_SHORT,        /* shorter last tile */
+    PP_ARM_STALL_SRC_CHANGE,        /* source index changes inside a tile */
+    PP_ARM_STALL_BLACK,             /* black source frame */
+    PP_ARM_STALL_NO_SPINNER,        /* frame without a spinner */
+    PP_ARM_STALL_SPIN_LEFT,         /* chunk across the spinner's left edge */
+    PP_ARM_STALL_SPIN_RIGHT,        /* ... its right edge */
+    PP_ARM_STALL_SPIN_INSIDE,       /* chunk wholly inside the spinner */
+    PP_ARM_STALL_SPIN_CLIPPED,      /* spinner larger than the frame */
+    PP_ARM_STALL_LAUNCH_SPLIT,      /* more than 256 frames: several launches */
+    PP_ARM_COUNT
+};
+#define PP_PACK_OP_PAD 0
+#define PP_PACK_OP_CPVS 1
+#define PP_PACK_OP_V210 2
+#define PP_PACK_OP_STALL 3
+/* kernel instances, the return value of the walker */
+#define PP_PACK_INST_CPVS8_420 0
+#define PP_PACK_INST_CPVS8_422 1
+#define PP_PACK_INST_CPVS10_420 2
+#define PP_PACK_INST_CPVS10_422 3
+#define PP_PACK_INST_PAD8 4
+#define PP_PACK_INST_PAD16 5
+#define PP_PACK_INST_STALL8 6
+#define PP_PACK_INST_STALL16 7
+/* One launch as the execute call would receive it.  src / dst carry only the
+ * alignment facts (addresses, line sizes, frame strides); for PP_PACK_OP_V210
+ * W, H, x, y are ignored; the stall fields are read for PP_PACK_OP_STALL only
+ * (spin_n frames of spin_w x spin_h uploaded for `fmt`, spin_n = 0: none). */
+typedef struct pp_pack_query {
+    int op, fmt, w, h, W, H, x, y, nframes;
+    pp_frames src, dst;
+    const int32_t *src_index, *spinner_index;
+    int spin_n, spin_w, spin_h;
+} pp_pack_query;
+/* Returns the kernel instance (PP_PACK_INST_*) and sets *arms, or returns the
+ * error the execute call returns for this launch (same code, same message).
+ * Added without raising PP_ABI_VERSION (still 7). */
+int pp_pack_arms(const pp_pack_query *q, uint64_t *arms);
 
 /* ---- P.910 SI/TI (spec PP-SITI-1) ------------------------
  * New feature behind util/SRC_analysis.py:120-147 (analyse_src) and

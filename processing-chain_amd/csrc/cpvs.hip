@@ -28,6 +28,7 @@
 
 #include "common.hpp"
 #include "filters.hpp"
+#include "pack_plan.hpp"
 
 namespace pp {
 
@@ -49,9 +50,8 @@ struct CpvsArgs {
     int aligned;          // all source rows 16-B aligned (vector staging)
 };
 
-constexpr int kCpvsLanes = 64;  // one wave per canvas row (4-wave rows: 2.05 vs 1.64 ms, v210 1080p)
-constexpr int kCpvsTaps = 4;    // bicubic 2x chroma: at most 4 rows per output row
-constexpr int kStageUnroll = 8; // 16-B staging loads a lane keeps in flight
+// Launch geometry, lane and tap counts and every path condition below are
+// pack_plan.hpp's (shared with the host and the arm walker).
 
 // DEPTH 8 -> uyvy422, DEPTH 10 -> v210.  V420: source chroma is 4:2:0.
 template <int DEPTH, bool V420>
@@ -65,7 +65,7 @@ __global__ __launch_bounds__(kCpvsLanes) void cpvs_kernel(const CpvsArgs a) {
     const int lane = threadIdx.x;
     const int by = 16 << (DEPTH - 8), bc = 128 << (DEPTH - 8);
     const int iy = y - a.oy;
-    const bool live = iy >= 0 && iy < a.h;
+    const bool live = row_live(iy, a.h);
     if (live) {
         // LDS = [Y | U | V] rows, each padded to whole 16-B groups: one index
         // space of 16-B pieces over the planes staged (Y only for 4:2:0, whose
@@ -74,9 +74,9 @@ __global__ __launch_bounds__(kCpvsLanes) void cpvs_kernel(const CpvsArgs a) {
         const uint8_t *row1 = a.src[1] + frame * a.sfs[1] + (int64_t)iy * a.sls[1];
         const uint8_t *row2 = a.src[2] + frame * a.sfs[2] + (int64_t)iy * a.sls[2];
         if (a.aligned) {
-            const int ny = a.ys * (int)sizeof(T) / 16, nc = V420 ? 0 : a.cs * (int)sizeof(T) / 16;
+            const int ny = cpvs_stage_luma(a.ys, (int)sizeof(T)), nc = cpvs_stage_chroma(a.cs, (int)sizeof(T), V420);
             const int total = ny + 2 * nc;
-            for (int base = 0; base < total; base += kCpvsLanes * kStageUnroll) {
+            for (int base = 0; base < total; base += kCpvsStagePass) {
                 uint4 r[kStageUnroll];
 #pragma unroll
                 for (int u = 0; u < kStageUnroll; ++u) {
@@ -117,7 +117,7 @@ __global__ __launch_bounds__(kCpvsLanes) void cpvs_kernel(const CpvsArgs a) {
 #pragma unroll
         for (int k = 0; k < kCpvsTaps; ++k) {
             const int r = p0 + k - coy;  // AVPVS chroma row, or outside -> black
-            const bool in = k < a.vt && r >= 0 && r < a.ch;
+            const bool in = cpvs_tap_in(k, a.vt, r, a.ch);
             coef[k] = k < a.vt ? vc[k] : 0;
             ur[k] = in ? a.src[1] + frame * a.sfs[1] + (int64_t)r * a.sls[1] : nullptr;
             vr[k] = in ? a.src[2] + frame * a.sfs[2] + (int64_t)r * a.sls[2] : nullptr;
@@ -129,13 +129,13 @@ __global__ __launch_bounds__(kCpvsLanes) void cpvs_kernel(const CpvsArgs a) {
         const uint32_t blackw = sizeof(T) == 2 ? (uint32_t)bc * 0x00010001u : (uint32_t)bc * 0x01010101u;
         const v2i16 c01 = {static_cast<int16_t>(coef[0]), static_cast<int16_t>(coef[1])};
         const v2i16 c23 = {static_cast<int16_t>(coef[2]), static_cast<int16_t>(coef[3])};
-        const int ngroups = (a.cw + 7) / 8;
-        const int nfull = a.aligned ? (a.cs / 8) : 0;  // groups inside the 16-B padded row
+        const int ngroups = cpvs_groups(a.cw);
+        const bool gvec = cpvs_group_vec(a.aligned);  // every group lies inside the 16-B padded row
         for (int g = lane; g < ngroups; g += kCpvsLanes) {
             uint32_t wu[kCpvsTaps][D], wv[kCpvsTaps][D];
 #pragma unroll
             for (int k = 0; k < kCpvsTaps; ++k) {
-                if (ur[k] && g < nfull) {
+                if (ur[k] && gvec) {
                     if constexpr (D == 4) {
                         const uint4 qu = reinterpret_cast<const uint4 *>(ur[k])[g];
                         const uint4 qv = reinterpret_cast<const uint4 *>(vr[k])[g];
@@ -147,12 +147,12 @@ __global__ __launch_bounds__(kCpvsLanes) void cpvs_kernel(const CpvsArgs a) {
                         wu[k][0] = qu.x; wu[k][1] = qu.y;
                         wv[k][0] = qv.x; wv[k][1] = qv.y;
                     }
-                } else if (ur[k]) {  // ragged tail or unaligned rows: sample by sample
+                } else if (ur[k]) {  // unaligned rows: sample by sample
 #pragma unroll
                     for (int d = 0; d < D; ++d) wu[k][d] = wv[k][d] = 0;
 #pragma unroll
                     for (int e = 0; e < 8; ++e) {
-                        const int x = min(g * 8 + e, a.cw - 1);
+                        const int x = cpvs_group_sample(g, e, a.cw);
                         constexpr int PER = 4 / (int)sizeof(T);
                         const int sh = 8 * (int)sizeof(T) * (e % PER);
                         wu[k][e / PER] |= (uint32_t)reinterpret_cast<const T *>(ur[k])[x] << sh;
@@ -200,19 +200,19 @@ __global__ __launch_bounds__(kCpvsLanes) void cpvs_kernel(const CpvsArgs a) {
     }
     __syncthreads();
     const int cox = a.ox >> 1;
-    constexpr int PX = DEPTH == 8 ? 8 : 6;  // pixels per 16-B chunk
+    constexpr int PX = cpvs_px(DEPTH);  // pixels per 16-B chunk
     constexpr int CPX = PX / 2;
     uint8_t *drow = a.dst + frame * a.dfs + (int64_t)y * a.dls;
     const bool chroma_live = V420 || live;
     // 8-bit: a chunk wholly inside the AVPVS with the pad offset on an 8-px
     // grid reads its 8 Y and 4 + 4 chroma samples as 3 LDS words and
     // interleaves them with v_perm
-    const bool fast8 = DEPTH == 8 && (a.ox & 7) == 0;
+    const bool fast8 = cpvs_fast8(DEPTH, a.ox);
     for (int q = lane; q < a.chunks; q += kCpvsLanes) {
         const int x0 = q * PX;
         if constexpr (DEPTH == 8) {
             const int sx0 = x0 - a.ox, csx0 = x0 / 2 - cox;
-            if (fast8 && live && sx0 >= 0 && sx0 + 8 <= a.w && csx0 + 4 <= a.cw && x0 + 8 <= a.W) {
+            if (cpvs_fast8_chunk(fast8, live, x0, a.ox, a.w, a.cw, a.W)) {
                 const uint2 yy = *reinterpret_cast<const uint2 *>(ly + sx0);
                 const uint32_t uu = *reinterpret_cast<const uint32_t *>(lu + csx0);
                 const uint32_t vv = *reinterpret_cast<const uint32_t *>(lv + csx0);
@@ -243,7 +243,7 @@ __global__ __launch_bounds__(kCpvsLanes) void cpvs_kernel(const CpvsArgs a) {
             for (int i = 0; i < 4; ++i)
                 wv[i] = (uint32_t)U[i] | ((uint32_t)Y[2 * i] << 8) | ((uint32_t)V[i] << 16) | ((uint32_t)Y[2 * i + 1] << 24);
             uint8_t *d = drow + (int64_t)q * 16;
-            if (x0 + PX <= a.W) {
+            if (uyvy_chunk_full(x0, a.W)) {
                 *reinterpret_cast<uint4 *>(d) = uint4{wv[0], wv[1], wv[2], wv[3]};
             } else {
                 for (int i = 0; i < 2 * (a.W - x0); ++i) {  // selects, not a private array
@@ -253,23 +253,20 @@ __global__ __launch_bounds__(kCpvsLanes) void cpvs_kernel(const CpvsArgs a) {
             }
         } else {
             auto c10 = [](int v) -> uint32_t { return v < 4 ? 4u : (v > 1019 ? 1019u : (uint32_t)v); };
-            const int full = a.W / 6;
+            const int cls = v210_chunk(q, a.W);
             uint4 o = {0, 0, 0, 0};
-            if (q < full) {
+            if (cls == kV210Full) {
                 o.x = c10(U[0]) | (c10(Y[0]) << 10) | (c10(V[0]) << 20);
                 o.y = c10(Y[1]) | (c10(U[1]) << 10) | (c10(Y[2]) << 20);
                 o.z = c10(V[1]) | (c10(Y[3]) << 10) | (c10(U[2]) << 20);
                 o.w = c10(Y[4]) | (c10(V[2]) << 10) | (c10(Y[5]) << 20);
-            } else if (q == full) {  // v210_enc_10 tail, w % 6 in {2..5}
-                const int r = a.W - 6 * full;
-                if (r >= 2) {
-                    o.x = c10(U[0]) | (c10(Y[0]) << 10) | (c10(V[0]) << 20);
-                    const uint32_t val = c10(Y[1]);
-                    if (r == 2) o.y = val;
-                    if (r >= 4) {
-                        o.y = val | (c10(U[1]) << 10) | (c10(Y[2]) << 20);
-                        o.z = c10(V[1]) | (c10(Y[3]) << 10);
-                    }
+            } else if (cls != kV210Zero) {  // v210_enc_10 tail, w % 6 in {2, 4} (w is even)
+                o.x = c10(U[0]) | (c10(Y[0]) << 10) | (c10(V[0]) << 20);
+                const uint32_t val = c10(Y[1]);
+                if (cls == kV210Tail2) o.y = val;
+                if (cls == kV210Tail4) {
+                    o.y = val | (c10(U[1]) << 10) | (c10(Y[2]) << 20);
+                    o.z = c10(V[1]) | (c10(Y[3]) << 10);
                 }
             }
             *reinterpret_cast<uint4 *>(drow + (int64_t)q * 16) = o;
@@ -283,9 +280,7 @@ using namespace pp;
 
 namespace {
 
-// Bicubic 4:2:0 -> 4:2:2 chroma rows of the CLI's auto-inserted converter
-// (sws_init_context with chrSrcH = ceil(H/2), chrDstH = H, centred siting),
-// compacted; kept per (H) in the context.
+// cpvs_vfilter's rows, compacted; kept per (H) in the context.
 struct VTab {
     int vt = 0;
     void *dev = nullptr;
@@ -299,21 +294,15 @@ int get_vtab(pp_ctx *ctx, int H, VTab **out) {
         *out = &it->second;
         return PP_OK;
     }
-    const int csh = ceil_rshift(H, 1);
-    const int inc = (int)((((int64_t)csh << 16) + (H >> 1)) / H);
-    FilterBank fb;
-    FilterBank::Compact c;
-    std::string err;
-    if (fb.build(inc, csh, H, 2, 1 << 12, PP_SWS_BICUBIC, PP_SWS_PARAM_DEFAULT, PP_SWS_PARAM_DEFAULT, local_pos(1),
-                 local_pos(0), &err) ||
-        fb.compact(csh, 1, &c, &err))
-        PP_FAIL(PP_ERR_UNSUPPORTED, "cpvs chroma filter: %s", err.c_str());
     VTab t;
-    t.vt = c.taps;
+    std::vector<int32_t> pos;
+    std::vector<int16_t> coef;
+    const int rc = cpvs_vfilter(H, &t.vt, &pos, &coef);
+    if (rc) return rc;
     const size_t pb = ((size_t)H * 4 + 255) & ~size_t(255);
-    std::vector<uint8_t> host(pb + c.coef.size() * 2);
-    std::memcpy(host.data(), c.pos.data(), (size_t)H * 4);
-    std::memcpy(host.data() + pb, c.coef.data(), c.coef.size() * 2);
+    std::vector<uint8_t> host(pb + coef.size() * 2);
+    std::memcpy(host.data(), pos.data(), (size_t)H * 4);
+    std::memcpy(host.data() + pb, coef.data(), coef.size() * 2);
     PP_HIP(hipMalloc(&t.dev, host.size()));
     PP_HIP(hipMemcpy(t.dev, host.data(), host.size(), hipMemcpyHostToDevice));
     auto res = g_vtabs.emplace(key, t);
@@ -325,22 +314,11 @@ int get_vtab(pp_ctx *ctx, int H, VTab **out) {
 
 extern "C" int pp_cpvs_execute(pp_ctx *ctx, int src_fmt, int w, int h, const pp_frames *src, int W, int H, int x,
                                int y, int out_fmt, const pp_frames *dst, int nframes, void *stream) {
-    if (!ctx || !src || !dst || nframes < 0) PP_FAIL(PP_ERR_INVALID, "null argument");
-    const FmtInfo fi = fmt_info(src_fmt);
-    if (!fi.valid || fi.packed || fi.hsub != 1) PP_FAIL(PP_ERR_INVALID, "cpvs source must be 4:2:0 or 4:2:2 planar");
-    if (out_fmt == PP_FMT_UYVY422 ? fi.depth != 8 : out_fmt == PP_FMT_V210 ? fi.depth != 10 : true)
-        PP_FAIL(PP_ERR_INVALID, "cpvs: uyvy422 needs an 8-bit AVPVS, v210 a 10-bit one");
-    if (W < w || H < h || (out_fmt == PP_FMT_UYVY422 && (W & 1))) PP_FAIL(PP_ERR_INVALID, "bad canvas %dx%d", W, H);
-    if (x < 0) x = (W - w) / 2;
-    if (y < 0) y = (H - h) / 2;
-    x = (x >> fi.hsub) << fi.hsub;
-    y = (y >> fi.vsub) << fi.vsub;
-    if (x + w > W || y + h > H) PP_FAIL(PP_ERR_INVALID, "input exceeds the canvas");
-    const int64_t line = out_fmt == PP_FMT_V210 ? pp_v210_linesize(W) : 2LL * W;
-    if (dst->linesize[0] < line || ((uintptr_t)dst->data[0] & 15) || (dst->linesize[0] & 15) ||
-        (nframes > 1 && (dst->frame_stride[0] & 15)))
-        PP_FAIL(PP_ERR_INVALID, "cpvs destination must be 16-B aligned with linesize >= %lld", (long long)line);
-    if (nframes == 0) return PP_OK;
+    if (!ctx) PP_FAIL(PP_ERR_INVALID, "null argument");
+    CpvsGeom g;
+    const int rc = cpvs_geometry(src_fmt, w, h, src, W, H, x, y, out_fmt, dst, nframes, &g);
+    if (rc || g.empty) return rc;
+    const FmtInfo fi = g.fi;
     PP_HIP(hipSetDevice(ctx->device));
     CpvsArgs a{};
     for (int p = 0; p < 3; ++p) {
@@ -351,28 +329,21 @@ extern "C" int pp_cpvs_execute(pp_ctx *ctx, int src_fmt, int w, int h, const pp_
     a.dst = (uint8_t *)dst->data[0];
     a.dls = dst->linesize[0];
     a.dfs = dst->frame_stride[0];
-    a.w = w; a.h = h; a.cw = ceil_rshift(w, 1); a.ch = ceil_rshift(h, fi.vsub);
-    a.W = W; a.H = H; a.ox = x; a.oy = y;
-    a.chunks = (int)(out_fmt == PP_FMT_V210 ? line / 16 : (W + 7) / 8);
+    a.w = g.w; a.h = g.h; a.cw = g.cw; a.ch = g.ch;
+    a.W = g.W; a.H = g.H; a.ox = g.ox; a.oy = g.oy;
+    a.chunks = g.chunks;
     if (fi.vsub) {
         VTab *t;
         int rc = get_vtab(ctx, H, &t);
         if (rc) return rc;
         a.vt = t->vt;
-        if (a.vt > kCpvsTaps) PP_FAIL(PP_ERR_UNSUPPORTED, "cpvs chroma filter of %d taps", a.vt);
         a.vpos = static_cast<const int32_t *>(t->dev);
         a.vcoef = reinterpret_cast<const int16_t *>(static_cast<const uint8_t *>(t->dev) + (((size_t)H * 4 + 255) & ~size_t(255)));
     }
-    const int es = fi.depth > 8 ? 2 : 1;
-    a.ys = (int)(((int64_t)w * es + 15) / 16 * 16 / es);
-    a.cs = (int)(((int64_t)a.cw * es + 15) / 16 * 16 / es);
-    a.aligned = 1;
-    for (int p = 0; p < 3; ++p)
-        if (((uintptr_t)src->data[p] & 15) || (src->linesize[p] & 15) || (nframes > 1 && (src->frame_stride[p] & 15)))
-            a.aligned = 0;
-    const size_t lds = (size_t)(a.ys + 2 * a.cs) * es;
-    if (lds > 64 * 1024) PP_FAIL(PP_ERR_UNSUPPORTED, "cpvs: AVPVS width %d exceeds the LDS row stage", w);
-    if ((int64_t)H * nframes >= (int64_t)1 << 31) PP_FAIL(PP_ERR_UNSUPPORTED, "cpvs: too many rows in one call");
+    a.ys = g.ys;
+    a.cs = g.cs;
+    a.aligned = g.aligned;
+    const size_t lds = g.lds;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 grid((unsigned)(H * nframes));
     if (fi.depth == 8 && fi.vsub)

@@ -16,25 +16,12 @@
 #include <vector>
 
 #include "common.hpp"
+#include "pack_plan.hpp"
 
 namespace pp {
 
-constexpr int kRowLanes = 64;  // one wave per row
-constexpr int kRowUnroll = 4;  // 16-B chunks a lane keeps in flight
-
-// Per-plane geometry of a row kernel launch.
-struct RowPlane {
-    const uint8_t *src;
-    int64_t sls, sfs;
-    uint8_t *dst;
-    int64_t dls, dfs;
-    int W, rows;       // output plane width (samples) and rows
-    int iw, ih;        // source plane size
-    int ox, oy;        // source offset on the output plane (pad); 0 for stall
-    int black;
-    int vec;           // source rows 16-B aligned and ox * EB % 16 == 0: vector loads
-    int dvec;          // destination rows 16-B aligned: vector stores
-};
+// The conditions that pick a path here (vector or sample-by-sample chunk
+// loads and stores, live rows, spinner overlap) are pack_plan.hpp's.
 
 // 16-B chunk of output samples [x, x + N) of a row: the source row shifted by
 // ox, black outside [0, iw) (and for a null row).
@@ -42,7 +29,7 @@ template <typename T>
 __device__ inline uint4 shifted_chunk(const T *srow, int x, int ox, int iw, int black, bool vec) {
     constexpr int N = 16 / (int)sizeof(T);
     const int sx = x - ox;
-    if (srow && vec && sx >= 0 && sx + N <= iw) return *reinterpret_cast<const uint4 *>(srow + sx);
+    if (chunk_src_vec(srow != nullptr, vec, sx, N, iw)) return *reinterpret_cast<const uint4 *>(srow + sx);
     T v[N];
 #pragma unroll
     for (int e = 0; e < N; ++e) v[e] = (srow && sx + e >= 0 && sx + e < iw) ? srow[sx + e] : static_cast<T>(black);
@@ -54,14 +41,14 @@ __device__ inline uint4 shifted_chunk(const T *srow, int x, int ox, int iw, int 
 template <typename T>
 __device__ inline void put_chunk(T *drow, int x, int W, bool dvec, const uint4 &v) {
     constexpr int N = 16 / (int)sizeof(T);
-    if (dvec && x + N <= W) {
+    if (chunk_dst_vec(dvec, x, N, W)) {
         *reinterpret_cast<uint4 *>(drow + x) = v;
     } else {
         T e[N];
         __builtin_memcpy(e, &v, 16);
 #pragma unroll
         for (int i = 0; i < N; ++i)
-            if (x + i < W) drow[x + i] = e[i];
+            if (chunk_sample_stored(x + i, W)) drow[x + i] = e[i];
     }
 }
 
@@ -89,11 +76,11 @@ __global__ __launch_bounds__(kRowLanes) void pad_kernel(const PadArgs a) {
     row_unit(xcd_remap(blockIdx.x, gridDim.x), a.pl, frame, p, y);
     const RowPlane &g = a.pl[p];
     const int iy = y - g.oy;
-    const T *srow = (iy >= 0 && iy < g.ih) ? reinterpret_cast<const T *>(g.src + frame * g.sfs + (int64_t)iy * g.sls)
+    const T *srow = row_live(iy, g.ih) ? reinterpret_cast<const T *>(g.src + frame * g.sfs + (int64_t)iy * g.sls)
                                            : nullptr;
     T *drow = reinterpret_cast<T *>(g.dst + frame * g.dfs + (int64_t)y * g.dls);
-    const int chunks = (g.W + N - 1) / N;
-    for (int q0 = threadIdx.x; q0 < chunks; q0 += kRowLanes * kRowUnroll) {
+    const int chunks = row_chunks(g.W, N);
+    for (int q0 = threadIdx.x; q0 < chunks; q0 += kRowPass) {
         uint4 v[kRowUnroll];
 #pragma unroll
         for (int u = 0; u < kRowUnroll; ++u) {
@@ -115,16 +102,13 @@ __global__ __launch_bounds__(kRowLanes) void pad_kernel(const PadArgs a) {
 // copied.  Spinner frame s: Y[sw*sh] Al[sw*sh] U V Ac[(sw>>hs)*(sh>>vs)] u16.
 struct StallArgs {
     RowPlane pl[3];
-    int32_t idx[2 * 256];  // per output frame of this launch: src index, spinner index
+    int32_t idx[2 * kStallLaunchFrames];  // per output frame of this launch: src index, spinner index
     const uint16_t *spin;  // spinner frames
     int64_t spin_stride;   // elements per spinner frame
     int hs, vs, sw, sh, ox, oy;
     int nk, G;             // output frames in this launch, frames per tile
 };
 
-#ifndef PIXPATH_STALL_G
-#define PIXPATH_STALL_G 6
-#endif
 template <int EB>
 __global__ __launch_bounds__(kRowLanes) void stall_kernel(const StallArgs a) {
     using T = typename std::conditional<EB == 1, uint8_t, uint16_t>::type;
@@ -150,9 +134,9 @@ __global__ __launch_bounds__(kRowLanes) void stall_kernel(const StallArgs a) {
     const int pw = p ? (a.sw >> a.hs) : a.sw, ph = p ? (a.sh >> a.vs) : a.sh;
     const int px0 = p ? (a.ox >> a.hs) : a.ox, py0 = p ? (a.oy >> a.vs) : a.oy;
     const int64_t ysz = (int64_t)a.sw * a.sh, csz = (int64_t)pw * ph;
-    const bool spin_row = y >= py0 && y < py0 + ph;
-    const int chunks = (g.W + N - 1) / N;
-    for (int q0 = threadIdx.x; q0 < chunks; q0 += kRowLanes * kRowUnroll) {
+    const bool spin_row = row_live(y - py0, ph);
+    const int chunks = row_chunks(g.W, N);
+    for (int q0 = threadIdx.x; q0 < chunks; q0 += kRowPass) {
         uint4 base[kRowUnroll];
         int cur = -2;  // no source row loaded (-1 is the black frame)
         for (int f = f0; f < f1; ++f) {
@@ -180,13 +164,13 @@ __global__ __launch_bounds__(kRowLanes) void stall_kernel(const StallArgs a) {
                 const int q = q0 + u * kRowLanes, x = q * N;
                 if (q >= chunks) continue;
                 uint4 v = base[u];
-                if (in_rows && x + N > px0 && x < px0 + pw) {
+                if (stall_chunk_blends(in_rows, x, N, px0, pw)) {
                     T e[N];
                     __builtin_memcpy(e, &v, 16);
 #pragma unroll
                     for (int i = 0; i < N; ++i) {
                         const int sx = x + i - px0;
-                        if (sx >= 0 && sx < pw) {
+                        if (stall_sample_blends(sx, pw)) {
                             const int al = A[sx];
                             e[i] = static_cast<T>((static_cast<int>(e[i]) * (255 - al) + static_cast<int>(S[sx]) * al + 127) / 255);
                         }
@@ -196,31 +180,6 @@ __global__ __launch_bounds__(kRowLanes) void stall_kernel(const StallArgs a) {
                 put_chunk<T>(drow, x, g.W, g.dvec, v);
             }
         }
-    }
-}
-
-// row-kernel plane geometry from the C-ABI frame descriptors
-inline void row_planes(RowPlane *pl, const FmtInfo &fi, const pp_frames *src, const pp_frames *dst, int nframes,
-                       int sw, int sh, int dw, int dh, int x, int y) {
-    const int es = fi.depth > 8 ? 2 : 1;
-    for (int p = 0; p < 3; ++p) {
-        const int hs = p ? fi.hsub : 0, vs = p ? fi.vsub : 0;
-        RowPlane &g = pl[p];
-        g.src = (const uint8_t *)src->data[p];
-        g.sls = src->linesize[p];
-        g.sfs = src->frame_stride[p];
-        g.dst = (uint8_t *)dst->data[p];
-        g.dls = dst->linesize[p];
-        g.dfs = dst->frame_stride[p];
-        g.W = ceil_rshift(dw, hs);
-        g.rows = ceil_rshift(dh, vs);
-        g.iw = ceil_rshift(sw, hs);
-        g.ih = ceil_rshift(sh, vs);
-        g.ox = x >> hs;
-        g.oy = y >> vs;
-        g.black = (p ? 128 : 16) << (fi.depth - 8);
-        g.vec = !((uintptr_t)g.src & 15) && !(g.sls & 15) && (nframes < 2 || !(g.sfs & 15)) && !((g.ox * es) & 15);
-        g.dvec = !((uintptr_t)g.dst & 15) && !(g.dls & 15) && (nframes < 2 || !(g.dfs & 15));
     }
 }
 
@@ -249,30 +208,24 @@ using namespace pp;
 
 extern "C" int pp_pad_execute(pp_ctx *ctx, int fmt, int sw, int sh, const pp_frames *src, int dw, int dh, int x,
                               int y, const pp_frames *dst, int nframes, void *stream) {
-    if (!ctx || !src || !dst || nframes < 0) PP_FAIL(PP_ERR_INVALID, "null argument");
-    const FmtInfo fi = fmt_info(fmt);
-    if (!fi.valid || fi.packed) PP_FAIL(PP_ERR_INVALID, "pad needs a planar format");
-    if (x < 0) x = (dw - sw) / 2;  // (ow-iw)/2, truncated like the expression's int conversion
-    if (y < 0) y = (dh - sh) / 2;
-    x = (x >> fi.hsub) << fi.hsub;  // ff_draw_round_to_sub(.., -1, ..)
-    y = (y >> fi.vsub) << fi.vsub;
-    if (x + sw > dw || y + sh > dh) PP_FAIL(PP_ERR_INVALID, "input %dx%d at (%d,%d) exceeds %dx%d", sw, sh, x, y, dw, dh);
-    if (nframes == 0) return PP_OK;
+    if (!ctx) PP_FAIL(PP_ERR_INVALID, "null argument");
+    PadGeom g;
+    const int rc = pad_geometry(fmt, sw, sh, src, dw, dh, x, y, dst, nframes, &g);
+    if (rc || g.empty) return rc;
     PP_HIP(hipSetDevice(ctx->device));
     PadArgs a{};
-    row_planes(a.pl, fi, src, dst, nframes, sw, sh, dw, dh, x, y);
-    const int64_t units = (int64_t)nframes * (a.pl[0].rows + a.pl[1].rows + a.pl[2].rows);
-    if (units >= ((int64_t)1 << 31)) PP_FAIL(PP_ERR_UNSUPPORTED, "pad: too many rows in one call");
+    for (int p = 0; p < 3; ++p) a.pl[p] = g.pl[p];
+    const unsigned units = (unsigned)nframes * (unsigned)(a.pl[0].rows + a.pl[1].rows + a.pl[2].rows);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (fi.depth > 8)
-        hipLaunchKernelGGL(pad_kernel<2>, dim3((unsigned)units), dim3(kRowLanes), 0, st, a);
+    if (g.fi.depth > 8)
+        hipLaunchKernelGGL(pad_kernel<2>, dim3(units), dim3(kRowLanes), 0, st, a);
     else
-        hipLaunchKernelGGL(pad_kernel<1>, dim3((unsigned)units), dim3(kRowLanes), 0, st, a);
+        hipLaunchKernelGGL(pad_kernel<1>, dim3(units), dim3(kRowLanes), 0, st, a);
     PP_HIP(hipGetLastError());
     return PP_OK;
 }
 
-extern "C" int64_t pp_v210_linesize(int w) { return (int64_t)((w + 47) / 48) * 48 * 8 / 3; }
+extern "C" int64_t pp_v210_linesize(int w) { return v210_linesize(w); }
 
 extern "C" int pp_v210_pack(pp_ctx *ctx, int w, int h, const pp_frames *src, const pp_frames *dst, int nframes,
                             void *stream) {
@@ -326,32 +279,25 @@ extern "C" int pp_spinner_upload(pp_ctx *ctx, int fmt, const uint8_t *rgba, int 
 
 extern "C" int pp_stall_compose(pp_ctx *ctx, int fmt, int w, int h, const pp_frames *src, const int32_t *src_index,
                                 const int32_t *spinner_index, const pp_frames *dst, int nframes, void *stream) {
-    if (!ctx || !src || !dst || !src_index || !spinner_index || nframes < 0) PP_FAIL(PP_ERR_INVALID, "null argument");
-    const FmtInfo fi = fmt_info(fmt);
-    if (!fi.valid || fi.packed) PP_FAIL(PP_ERR_INVALID, "stall compose needs a planar format");
-    if ((w & ((1 << fi.hsub) - 1)) || (h & ((1 << fi.vsub) - 1))) PP_FAIL(PP_ERR_INVALID, "odd frame size");
-    bool need_spin = false;
-    for (int k = 0; k < nframes; ++k) need_spin |= spinner_index[k] >= 0;
-    if (need_spin && (ctx->spin_fmt != fmt || !ctx->spin_buf))
-        PP_FAIL(PP_ERR_INVALID, "no spinner uploaded for format %d", fmt);
-    for (int k = 0; k < nframes; ++k)
-        if (spinner_index[k] >= ctx->spin_n) PP_FAIL(PP_ERR_INVALID, "spinner index %d out of range", spinner_index[k]);
-    if (nframes == 0) return PP_OK;
+    if (!ctx) PP_FAIL(PP_ERR_INVALID, "null argument");
+    StallGeom g;
+    const int rc = stall_geometry(fmt, w, h, src, src_index, spinner_index, dst, nframes,
+                                  ctx->spin_buf ? ctx->spin_fmt : -1, ctx->spin_n, ctx->spin_w, ctx->spin_h, &g);
+    if (rc || g.empty) return rc;
+    const FmtInfo fi = g.fi;
     hipStream_t st = static_cast<hipStream_t>(stream);
     PP_HIP(hipSetDevice(ctx->device));
     StallArgs a{};
-    row_planes(a.pl, fi, src, dst, nframes, w, h, w, h, 0, 0);
+    for (int p = 0; p < 3; ++p) a.pl[p] = g.pl[p];
     a.spin = static_cast<const uint16_t *>(ctx->spin_buf);
     const int cw = ctx->spin_w >> fi.hsub, ch = ctx->spin_h >> fi.vsub;
     a.spin_stride = 2 * (int64_t)ctx->spin_w * ctx->spin_h + 3 * (int64_t)cw * ch;
     a.hs = fi.hsub; a.vs = fi.vsub;
-    a.sw = need_spin ? ctx->spin_w : 0; a.sh = need_spin ? ctx->spin_h : 0;
-    a.ox = ((w - a.sw) / 2) >> fi.hsub << fi.hsub;
-    a.oy = ((h - a.sh) / 2) >> fi.vsub << fi.vsub;
+    a.sw = g.sw; a.sh = g.sh; a.ox = g.ox; a.oy = g.oy;
     const int rows = a.pl[0].rows + a.pl[1].rows + a.pl[2].rows;
-    // frame indices travel in the kernel arguments, 256 output frames per launch
-    for (int k0 = 0; k0 < nframes; k0 += 256) {
-        const int nk = std::min(256, nframes - k0);
+    // frame indices travel in the kernel arguments, kStallLaunchFrames output frames per launch
+    for (int k0 = 0; k0 < nframes; k0 += kStallLaunchFrames) {
+        const int nk = std::min(kStallLaunchFrames, nframes - k0);
         for (int k = 0; k < nk; ++k) {
             a.idx[2 * k] = src_index[k0 + k];
             a.idx[2 * k + 1] = spinner_index[k0 + k];
@@ -359,11 +305,7 @@ extern "C" int pp_stall_compose(pp_ctx *ctx, int fmt, int w, int h, const pp_fra
         StallArgs b = a;
         for (int p = 0; p < 3; ++p) b.pl[p].dst += k0 * a.pl[p].dfs;
         b.nk = nk;
-        // frames per wave (one source load, G stores of the row).  Round 2,
-        // one wave per (row, frame) in tiles of G: G = 1 1.34 ms, 2
-        // 1.09-1.12, 3 1.07-1.10, 4 1.12, 6 1.03-1.05, 8 1.33, 16 1.42, 64 1.55
-        // (power-of-two tiles alias the frames' rows onto the same HBM channels)
-        b.G = PIXPATH_STALL_G;
+        b.G = g.G;  // frames per wave (one source load, G stores of the row): pack_plan.cpp
         const dim3 grid((unsigned)((nk + b.G - 1) / b.G * rows));
         if (fi.depth > 8)
             hipLaunchKernelGGL(stall_kernel<2>, grid, dim3(kRowLanes), 0, st, b);

@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from . import formats
+from . import _native
 from ._native import check, lib
 from .frames import FrameBatch
 
@@ -279,6 +280,57 @@ def stall_compose(src, src_index, spinner_index, dst=None, stream=None):
     check(lib().pp_stall_compose(ctx.handle, src.fmt.id, src.w, src.h, ctypes.byref(s), si.ctypes.data,
                                  sp.ctypes.data, ctypes.byref(d), si.size, _stream(src.planes[0], stream)))
     return dst
+
+
+# enum pp_pack_arm (include/pixpath.h), by value, and the PP_PACK_OP_* / PP_PACK_INST_* values
+PACK_ARMS = (
+    "cpvs_row_live", "cpvs_row_pad", "cpvs_stage_vec_one", "cpvs_stage_vec_multi", "cpvs_stage_samples",
+    "cpvs_group_vec", "cpvs_group_samples", "cpvs_group_clamped", "cpvs_group_vec_ragged", "cpvs_tap_above",
+    "cpvs_tap_below", "cpvs_groups_gt64", "cpvs_c8_fast", "cpvs_c8_offgrid", "cpvs_c8_slow_full", "cpvs_c8_slow_tail",
+    "cpvs_v210_full", "cpvs_v210_tail2", "cpvs_v210_tail4", "cpvs_v210_zero", "cpvs_chunks_gt64",
+    "row_src_vec", "row_src_edge", "row_src_outside", "row_src_scalar", "row_src_null", "row_dst_vec",
+    "row_dst_tail", "row_dst_scalar", "row_chunks_gt256", "row_420", "row_422", "row_444",
+    "stall_tile_full", "stall_tile_short", "stall_src_change", "stall_black", "stall_no_spinner",
+    "stall_spin_left", "stall_spin_right", "stall_spin_inside", "stall_spin_clipped", "stall_launch_split")
+PACK_OPS = ("pad", "cpvs", "v210", "stall")
+PACK_INSTANCES = ("cpvs8_420", "cpvs8_422", "cpvs10_420", "cpvs10_422", "pad8", "pad16", "stall8", "stall16")
+
+
+def _layout_struct(layout):
+    """pp_frames from a FrameBatch or from alignment facts (data[3], linesize[3], frame_stride[3])."""
+    if hasattr(layout, "frames_struct"):
+        return layout.frames_struct()
+    s = _native.pp_frames()
+    for p in range(3):
+        s.data[p], s.linesize[p], s.frame_stride[p] = (int(v[p]) for v in layout)
+    return s
+
+
+def pack_arms(op, fmt, w, h, src, dst, W=None, H=None, x=-1, y=-1, nframes=1, src_index=None, spinner_index=None,
+              spinner=(0, 0, 0)):
+    """Which arms of the pad / stall row kernels or the fused CPVS kernel one
+    launch executes (pp_pack_arms): host only, no GPU.  op: "pad", "cpvs",
+    "v210" or "stall"; src / dst: the batches, or their alignment facts as
+    (data[3], linesize[3], frame_stride[3]); spinner: (frames, width, height)
+    uploaded for ``fmt``.  Returns (kernel instance, frozenset of arm names);
+    a launch the execute call rejects raises its PixpathError."""
+    q = _native.pp_pack_query()
+    q.op, q.fmt = PACK_OPS.index(op), formats.fmt(fmt).id
+    q.w, q.h = int(w), int(h)
+    q.W, q.H = int(w if W is None else W), int(h if H is None else H)
+    q.x, q.y, q.nframes = int(x), int(y), int(nframes)
+    q.src, q.dst = _layout_struct(src), _layout_struct(dst)
+    if op == "stall":
+        si = np.ascontiguousarray(src_index, dtype=np.int32)
+        sp = np.ascontiguousarray(spinner_index, dtype=np.int32)
+        if si.shape != sp.shape:
+            raise ValueError("index arrays differ in length")
+        q.nframes = si.size
+        q.src_index, q.spinner_index = si.ctypes.data, sp.ctypes.data
+        q.spin_n, q.spin_w, q.spin_h = (int(v) for v in spinner)
+    mask = ctypes.c_uint64()
+    inst = check(lib().pp_pack_arms(ctypes.byref(q), ctypes.byref(mask)))
+    return PACK_INSTANCES[inst], frozenset(a for i, a in enumerate(PACK_ARMS) if mask.value >> i & 1)
 
 
 def fps_map(n_in, in_rate, out_rate):
