@@ -201,6 +201,30 @@ int pp_cpvs_execute(pp_ctx *ctx, int src_fmt, int w, int h, const pp_frames *src
                     int W, int H, int x, int y, int out_fmt,
                     const pp_frames *dst, int nframes, void *stream);
 
+/* ---- CPVS unpackers ----------------------------------------------------
+ * Reads the payloads above back: a v210 or uyvy422 CPVS (to score it against
+ * its AVPVS with pp_metrics) or an uncompressed SRC (pp_siti on its luma).
+ * Inverse of the CPVS packers.  src: plane 0 of nframes W x H frames of
+ * in_fmt (PP_FMT_V210 or PP_FMT_UYVY422).  dst: the w x h window at (x, y)
+ * of each frame as planar 4:2:2 (yuv422p10le for v210, yuv422p for uyvy422).
+ * dst->data[1] == dst->data[2] == NULL: luma only.
+ * v210 (libavcodec/v210dec.c): little-endian 32-bit words of three 10-bit
+ * fields (bits 30-31 ignored), U0 Y0 V0 | Y1 U1 Y2 | V1 Y3 U2 | Y4 V2 Y5 per
+ * 16 bytes; the tails of W % 6 in {2, 4} are the same layout cut short.  W
+ * even; src linesize a multiple of 4 and >= ceil(W/6)*16 (it need not be
+ * pp_v210_linesize(W) nor 16-byte aligned).  uyvy422: bytes U Y0 V Y1; W
+ * even; linesize >= 2 W.  Window: 0 <= x, x even, x + w <= W, 0 <= y,
+ * y + h <= H, w >= 1 (may be odd: chroma width (w+1)/2), h >= 1; there is no
+ * -1 = centred shorthand: pass the offsets the pad put the picture at.
+ * Sources and destinations on the 16-byte grid (pointers, linesizes, frame
+ * strides) move as 16-byte loads and stores; anything else goes sample by
+ * sample with identical output.  Arguments are checked before any HIP call;
+ * nframes == 0 is PP_OK.  Parity with FFmpeg's v210dec / rawdec is unpinned.
+ * Added without raising PP_ABI_VERSION (still 7). */
+int pp_unpack_execute(pp_ctx *ctx, int in_fmt, int W, int H, const pp_frames *src,
+                      int x, int y, int w, int h, const pp_frames *dst,
+                      int nframes, void *stream);
+
 /* ---- stall compositing (spec PP-STALL-1) -----------------
  * Replaces the external `bufferer -s spinner.png` call at
  * p03_generateAvPvs.py:236-243.  Uploads one spinner animation (n RGBA8

@@ -16,7 +16,7 @@ ERRORS = {-1: "PP_ERR_INVALID", -2: "PP_ERR_HIP", -3: "PP_ERR_NOMEM", -4: "PP_ER
 EXPORTS = (
     "pp_abi_version", "pp_last_error", "pp_ctx_create", "pp_ctx_destroy", "pp_plane_bytes",
     "pp_v210_linesize", "pp_scale_plan_create", "pp_scale_chain_plan_create", "pp_scale_plan_destroy", "pp_scale_plan_filter",
-    "pp_scale_plan_path", "pp_scale_plan_stats", "pp_scale_plan_instances", "pp_scale_execute", "pp_pad_execute", "pp_v210_pack", "pp_cpvs_execute", "pp_spinner_upload", "pp_stall_compose",
+    "pp_scale_plan_path", "pp_scale_plan_stats", "pp_scale_plan_instances", "pp_scale_execute", "pp_pad_execute", "pp_v210_pack", "pp_cpvs_execute", "pp_unpack_execute", "pp_spinner_upload", "pp_stall_compose",
     "pp_siti", "pp_siti_ex", "pp_metrics", "pp_pack_arms", "pp_fps_map",
     "pp_device_alloc", "pp_device_free", "pp_host_alloc", "pp_host_free", "pp_stream_create",
     "pp_stream_destroy", "pp_stream_synchronize", "pp_event_create", "pp_event_destroy", "pp_event_record",
@@ -87,6 +87,7 @@ def lib():
         "pp_pad_execute": (i32, [vp, i32, i32, i32, fr, i32, i32, i32, i32, fr, i32, vp]),
         "pp_v210_pack": (i32, [vp, i32, i32, fr, fr, i32, vp]),
         "pp_cpvs_execute": (i32, [vp, i32, i32, i32, fr, i32, i32, i32, i32, i32, fr, i32, vp]),
+        "pp_unpack_execute": (i32, [vp, i32, i32, i32, fr, i32, i32, i32, i32, fr, i32, vp]),
         "pp_spinner_upload": (i32, [vp, i32, vp, i32, i32, i32]),
         "pp_stall_compose": (i32, [vp, i32, i32, i32, fr, vp, vp, fr, i32, vp]),
         "pp_siti": (i32, [vp, i32, i32, i32, vp, i64, i64, i32, vp, vp, vp, vp]),

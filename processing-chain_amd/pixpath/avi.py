@@ -211,12 +211,14 @@ class AviWriter:
                 os.remove(self.part)
 
 
-def scan(path):
+def scan(path, headers_only=False):
     """(info, index) of an AVI without loading it: info = {w, h, rate,
     handler, fourcc, extradata} of its first VIDEO stream ('vids' strl; an
     audio strl's strh/strf never overwrite it), index = [(file offset, size)]
     of that stream's packets in file order.  Chunks are walked with seeks, so
-    a tens-of-GB long-test AVPVS costs one 8-byte read per packet."""
+    a tens-of-GB long-test AVPVS costs one 8-byte read per packet.
+    headers_only: the 'movi' lists are skipped (index stays empty): what a
+    caller needs to choose a reader by fourcc."""
     info, index = {}, []
     with open(path, "rb") as fh:
         fh.seek(0, 2)
@@ -235,7 +237,8 @@ def scan(path):
                     if hdr[8:12] == b"strl":
                         state["strl"] += 1
                         state["type"] = None
-                    walk(body + 4, min(body + size, end))
+                    if not (headers_only and hdr[8:12] == b"movi"):
+                        walk(body + 4, min(body + size, end))
                 elif tag == b"strh":
                     fh.seek(body)
                     d = fh.read(min(size, 56))

@@ -13,7 +13,8 @@ the ffmpeg strings they replace).
   concat long-test segment AVIs -> one AVI, packets copied (create_avpvs_long_concat :1058, GPU-FFV1 AVIs)
   preview AVPVS decoded here (GPU FFV1) -> ffmpeg's ProRes (create_preview :1250)
   siti   P.910 SI/TI of a SRC (util/SRC_analysis.py hook)
-  metrics per-frame PSNR / SSIM of a PVS against its SRC (spec PP-METRIC-1; after p03)
+  metrics per-frame PSNR / SSIM of a PVS against its SRC (spec PP-METRIC-1; after p03);
+          --crop WxH [--avpvs-pix-fmt NAME] scores a v210 / UYVY CPVS against its AVPVS
 
 Inputs/outputs ending in .y4m or .raw/.yuv are read/written directly;
 anything else goes through ffmpeg pipes.  The device is PIXPATH_DEVICE, else
@@ -639,7 +640,15 @@ def cmd_siti(args):
 
 def cmd_metrics(args):
     from . import metrics
-    res = metrics.metrics_of_files(args.ref, args.input, batch=args.batch, flags=args.flags)
+    kw = {}
+    if args.crop:  # a CPVS canvas: compare the AVPVS picture inside it
+        cw, ch = args.crop.lower().split("x")
+        kw["crop"] = (int(cw), int(ch))
+        if args.avpvs_pix_fmt:
+            kw["crop_from"] = args.avpvs_pix_fmt
+    elif args.avpvs_pix_fmt:
+        raise SystemExit("--avpvs-pix-fmt needs --crop")
+    res = metrics.metrics_of_files(args.ref, args.input, batch=args.batch, flags=args.flags, **kw)
     print(json.dumps(metrics.report(res, args.ref, args.input, per_frame=args.per_frame)))
     return 0
 
@@ -742,6 +751,10 @@ def main(argv=None):
     p.add_argument("--batch", type=int, default=32)
     p.add_argument("--flags", default="bicubic", help="scaler bringing the SRC to the input's size and format")
     p.add_argument("--per-frame", action="store_true")
+    p.add_argument("--crop", default=None, metavar="WxH",
+                   help="the input is a v210 / UYVY CPVS: compare the WxH AVPVS picture inside its canvas")
+    p.add_argument("--avpvs-pix-fmt", default=None, metavar="NAME",
+                   help="pixel format of the AVPVS the CPVS was padded from (yuv420p...: rows offset rounded to even)")
     p.set_defaults(fn=cmd_metrics)
 
     args = ap.parse_args(argv)

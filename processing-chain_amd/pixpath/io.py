@@ -145,6 +145,80 @@ class FFmpegReader(RawReader):  # pragma: no cover - needs ffmpeg
             raise RuntimeError("ffmpeg decode failed")
 
 
+PACKED_FOURCC = {b"v210": "v210", b"uyvy": "uyvy422"}  # AVI video fourcc (lower case) -> packed format
+
+
+def packed_fourcc(fourcc):
+    """The packed format name of an AVI fourcc (compared case-insensitively), or None."""
+    return PACKED_FOURCC.get(bytes(fourcc or b"").lower())
+
+
+class PackedAviReader(Reader):
+    """An uncompressed AVI of v210 or UYVY packets, read without ffmpeg: the
+    CPVS files of create_cpvs (`-c:v v210`, `-c:v rawvideo -pix_fmt uyvy422`)
+    and SRCs stored that way.  The Reader interface over the PACKED format:
+    ``fmt`` is v210 or uyvy422, ``frame_bytes`` the packet size, and
+    read_into copies packets straight from the file (pixpath.avi.scan walks
+    the chunks, no index needed), so they go disk -> pinned -> HBM as they are
+    and ops.unpack re-lays them out on the GPU.  Every packet must have the
+    same size; any other fourcc raises ValueError.
+
+    ``linesize`` is packet size // h.  For v210 it must divide exactly, be a
+    multiple of 4 and >= ceil(w/6)*16: FFmpeg's encoder writes
+    formats.v210_linesize(w) (128-byte aligned), other strides are accepted
+    because v210dec's sample layout does not depend on the stride.  Which
+    strides FFmpeg itself infers for such a file is [EXT], unpinned (no FFmpeg
+    in this environment).  For uyvy422 it must be >= 2 w."""
+
+    def __init__(self, path):
+        from . import avi
+        info, index = avi.scan(path)
+        name = packed_fourcc(info.get("fourcc"))
+        if name is None:
+            raise ValueError("%s: fourcc %r is neither v210 nor UYVY" % (path, bytes(info.get("fourcc", b""))))
+        self.fmt = formats.fmt(name)
+        self.w, self.h, self.rate = int(info["w"]), int(info["h"]), Fraction(info["rate"])
+        need = (self.w + 5) // 6 * 16 if name == "v210" else 2 * self.w
+        sizes = sorted({s for _, s in index})
+        if len(sizes) > 1:
+            raise ValueError("%s: packets of %d and %d bytes (every frame must have the same size)"
+                             % (path, sizes[0], sizes[-1]))
+        size = sizes[0] if sizes else need * self.h
+        if self.h < 1 or size % self.h:
+            raise ValueError("%s: packet size %d is not a whole number of %d lines" % (path, size, self.h))
+        self.linesize = size // self.h
+        if self.linesize < need or (name == "v210" and self.linesize % 4):
+            raise ValueError("%s: line size %d, %s needs %s>= %d" % (path, self.linesize, name,
+                                                                    "a multiple of 4 " if name == "v210" else "", need))
+        self._size, self._index, self._next = size, index, 0
+        self.fh = open(path, "rb")
+
+    @property
+    def frame_bytes(self):
+        return self._size
+
+    def _read_frame(self, mv):
+        if self._next >= len(self._index):
+            return False
+        self.fh.seek(self._index[self._next][0])
+        if _readexact(self.fh, mv) != len(mv):
+            return False
+        self._next += 1
+        return True
+
+    def device_batch(self, storage):
+        """A packed FrameBatch over a [k, frame_bytes] uint8 device tensor of packets."""
+        from .frames import FrameBatch
+        k = storage.shape[0]
+        b = FrameBatch(self.fmt, self.w, self.h, k, device=storage.device,
+                       planes=[storage.view(k, self.h, self.linesize)])
+        b.storage = storage
+        return b
+
+    def close(self):
+        self.fh.close()
+
+
 class Writer:
     def write(self, frames_u8):
         """frames_u8: [k, frame_bytes] uint8 (or bytes-like of k dense frames)."""

@@ -72,17 +72,51 @@ def summarize(sse, ssim, fmt, w, h):
 
 
 def _open(path, batch):
-    from . import ffv1, io as pio
+    """The reader of a file: an AVI by its video fourcc (v210 / UYVY: the
+    packed reader, unpacked on the GPU by _read_device; anything else, FFV1
+    first of all, the FFV1 reader), other files through io.open_reader."""
+    from . import avi, ffv1, io as pio
     if path.lower().endswith(".avi"):
+        if pio.packed_fourcc(avi.scan(path, headers_only=True)[0].get("fourcc")):
+            return pio.PackedAviReader(path)
         return ffv1.open_avpvs_reader(path, batch=batch)
     return pio.open_reader(path)
 
 
-def _read_device(rd, n, device):
-    """Up to n frames of a reader as an interleaved device FrameBatch the caller owns, or None."""
+def planar_format(rd):
+    """The planar format _read_device delivers a reader's frames in."""
+    if rd.fmt.packed:
+        return formats.fmt("yuv422p10le" if rd.fmt.id == formats.V210 else "yuv422p")
+    return rd.fmt
+
+
+def crop_window(W, H, w, h, crop_from="yuv422p"):
+    """(x, y, w, h) of a w x h picture on the W x H canvas where the CPVS pad
+    put it: pad_offset's rule (csrc/pack_plan.hpp, pp_pad_execute with
+    x = y = -1) -- the centring expression (outer - inner) / 2 rounded down to
+    the chroma grid of the padded format ``crop_from`` (the AVPVS's: x to even
+    for 4:2:0 and 4:2:2, y to even for 4:2:0 only)."""
+    f = formats.fmt(crop_from)
+    w, h = int(w), int(h)
+    if w < 1 or h < 1 or w > W or h > H:
+        raise ValueError("crop %dx%d does not fit the %dx%d canvas" % (w, h, W, H))
+    return (((W - w) // 2) >> f.hsub) << f.hsub, (((H - h) // 2) >> f.vsub) << f.vsub, w, h
+
+
+def _read_device(rd, n, device, window=None):
+    """Up to n frames of a reader as a planar device FrameBatch the caller
+    owns, or None.  A packed reader's packets go to the GPU as they are and are
+    unpacked there (ops.unpack), to ``window`` (x, y, w, h) if given."""
     import torch
 
     from .frames import FrameBatch
+    if rd.fmt.packed:
+        from . import ops
+        host = np.empty((n, rd.frame_bytes), np.uint8)
+        k = rd.read_into(host, n)
+        if k == 0:
+            return None
+        return ops.unpack(rd.device_batch(torch.from_numpy(host[:k]).to(device)), crop=window)
     if hasattr(rd, "read_device"):
         b = rd.read_device(n)  # a view of the reader's own buffer
         if b is None:
@@ -106,7 +140,7 @@ def _map_entries(k0, n, in_rate, out_rate, n_in=None):
     return ops.fps_map(n_in, in_rate, out_rate)[k0:k0 + n]
 
 
-def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic"):
+def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, crop_from="yuv422p"):
     """PP-METRIC-1 of the file ``dist_path`` (the PVS) against ``ref_path``
     (the SRC); returns ``summarize``'s dict.  Both are read with the chain's
     own readers (FFV1 AVIs through ffv1.open_avpvs_reader, anything else
@@ -115,7 +149,15 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic"):
     another rate, distorted frame k is compared with the reference frame
     vf_fps would show there (ops.fps_map).  Frames stream through the GPU
     ``batch`` at a time; the comparison ends with the shorter of the distorted
-    clip and the rate-converted reference."""
+    clip and the rate-converted reference.
+
+    A v210 or UYVY AVI (a CPVS, or an uncompressed SRC) is read by
+    io.PackedAviReader and unpacked on the GPU (ops.unpack) to yuv422p10le /
+    yuv422p.  ``crop`` = (w, h): the distorted clip is a CPVS canvas and only
+    the w x h AVPVS picture inside it is compared, at the offsets the CPVS pad
+    put it (crop_window; ``crop_from``: the AVPVS's pixel format, which decides
+    the rounding of the offsets -- pass "yuv420p" / "yuv420p10le" for a 4:2:0
+    AVPVS).  Without ``crop`` the whole canvas is compared."""
     import torch
 
     from . import ops
@@ -124,14 +166,20 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic"):
     ref, dist = _open(ref_path, batch), _open(dist_path, batch)
     try:
         dev = torch.device("cuda", torch.cuda.current_device())
-        same = (ref.fmt.id, ref.w, ref.h) == (dist.fmt.id, dist.w, dist.h)
-        scaler = None if same else ops.Scaler(ref.fmt, ref.w, ref.h, dist.fmt, dist.w, dist.h, flags=flags,
-                                              device=dev)
+        window = None
+        if crop is not None:
+            if not dist.fmt.packed:
+                raise ValueError("crop applies to a packed (v210 / UYVY) distorted clip")
+            window = crop_window(dist.w, dist.h, crop[0], crop[1], crop_from)
+        rfmt, dfmt = planar_format(ref), planar_format(dist)
+        dw, dh = (dist.w, dist.h) if window is None else window[2:]
+        same = (rfmt.id, ref.w, ref.h) == (dfmt.id, dw, dh)
+        scaler = None if same else ops.Scaler(rfmt, ref.w, ref.h, dfmt, dw, dh, flags=flags, device=dev)
         in_rate, out_rate = ref.rate, dist.rate
         win, win0, n_ref, ref_end = None, 0, 0, False  # resident reference frames [win0, n_ref), dist geometry
         outs, k0 = [], 0
         while True:
-            d = _read_device(dist, batch, dev)
+            d = _read_device(dist, batch, dev, window)
             if d is None:
                 break
             m = _map_entries(k0, d.n, in_rate, out_rate)
@@ -147,7 +195,7 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic"):
                     win, win0 = r, n_ref
                 else:
                     k1 = win.n - keep
-                    nw = FrameBatch(dist.fmt, dist.w, dist.h, k1 + r.n, device=dev)
+                    nw = FrameBatch(dfmt, dw, dh, k1 + r.n, device=dev)
                     for p in range(3):
                         nw.view(p)[:k1].copy_(win.view(p)[keep:])
                         nw.view(p)[k1:].copy_(r.view(p))
@@ -158,8 +206,7 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic"):
             if len(m) == 0 or win is None:
                 break
             if len(m) < d.n:
-                d = FrameBatch.interleaved(dist.fmt, dist.w, dist.h, len(m), device=d.device,
-                                           storage=d.storage[:len(m)])
+                d = FrameBatch(dfmt, dw, dh, len(m), device=d.device, planes=[t[:len(m)] for t in d.planes])
             outs.append(ops.metrics(win, d, ref_index=m - win0))
             k0 += d.n
         torch.cuda.current_stream(dev).synchronize()
@@ -171,7 +218,7 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic"):
         ssim = torch.cat([o[1] for o in outs]).cpu().numpy()
     else:
         sse, ssim = np.zeros((0, 3), np.int64), np.zeros((0, 3))
-    return summarize(sse, ssim, dist.fmt, dist.w, dist.h)
+    return summarize(sse, ssim, dfmt, dw, dh)
 
 
 def _json_value(v):

@@ -200,6 +200,60 @@ def cpvs(src, W=None, H=None, out_fmt=None, x=-1, y=-1, dst=None, stream=None):
     return dst
 
 
+# unpack kernel geometry (csrc/unpack_plan.hpp), for tests that place sizes on its seams
+UNPACK_LANES = 64                          # kUnpackLanes: lanes of the one wave that owns a row
+UNPACK_UNROLL = 4                          # kUnpackUnroll: input chunks a lane decodes per trip of the row loop
+UNPACK_CHUNK_PX = {"v210": 6, "uyvy422": 8}  # unpack_px: pixels per 16-B input chunk (one chunk a lane at a time)
+UNPACK_PIECE_BYTES = 16                    # output granule: a lane stores one per trip of the store loop
+UNPACK_ROWS_PER_WORKGROUP = 1
+
+
+def unpack_trip_px(fmt):
+    """Pixels of a row one trip of the decode loop covers: a window wider than
+    this takes a second trip."""
+    return UNPACK_LANES * UNPACK_UNROLL * UNPACK_CHUNK_PX[formats.fmt(fmt).name]
+
+
+def unpack(src, crop=None, luma_only=False, dst=None, stream=None):
+    """v210 -> yuv422p10le / uyvy422 -> yuv422p (pp_unpack_execute), the inverse
+    of ``cpvs`` and ``v210_pack``.  ``src``: a FrameBatch of v210 or uyvy422
+    (its plane may have any pitch the format allows); ``crop``: the window
+    (x, y, w, h) to unpack, default the whole frame (x even).  Returns (or
+    fills) a planar FrameBatch of the window's size; with ``luma_only`` a
+    [N, h, w] luma tensor (uint16 / uint8, a pitched view) as ``siti`` takes,
+    and no chroma is written anywhere."""
+    if src.fmt.id not in (formats.V210, formats.UYVY422):
+        raise ValueError("unpack takes v210 or uyvy422, not %s" % src.fmt.name)
+    x, y, w, h = (0, 0, src.w, src.h) if crop is None else (int(v) for v in crop)
+    of = formats.fmt(formats.YUV422P10LE if src.fmt.id == formats.V210 else formats.YUV422P)
+    ctx = context(src.device.index)
+    s = src.frames_struct()
+    if luma_only:
+        es = of.bytes_per_sample
+        if dst is None:
+            pitch = (max(w, 1) * es + 15) // 16 * 16 // es
+            dst = torch.empty((src.n, max(h, 1), pitch), dtype=torch.uint16 if es == 2 else torch.uint8,
+                              device=src.device)[:, :h, :w]
+        if dst.dim() != 3 or tuple(dst.shape[1:]) != (h, w) or dst.shape[0] < src.n or dst.element_size() != es \
+                or (w > 1 and dst.stride(2) != 1):
+            raise ValueError("luma destination must be a [N, %d, %d] tensor of %d-byte samples" % (h, w, es))
+        d = _native.pp_frames()
+        d.data[0] = dst.data_ptr()
+        d.linesize[0] = dst.stride(1) * es
+        d.frame_stride[0] = dst.stride(0) * es
+        t = dst
+    else:
+        if dst is None:
+            dst = FrameBatch(of, w, h, src.n, device=src.device)
+        if (dst.fmt.id, dst.w, dst.h) != (of.id, w, h) or dst.n < src.n:
+            raise ValueError("destination batch does not match the window")
+        d = dst.frames_struct()
+        t = dst.planes[0]
+    check(lib().pp_unpack_execute(ctx.handle, src.fmt.id, src.w, src.h, ctypes.byref(s), x, y, w, h, ctypes.byref(d),
+                                  src.n, _stream(t, stream)))
+    return dst
+
+
 def siti(luma, bitdepth, prev=None, stream=None, normalize=False):
     """Per-frame P.910 SI/TI of a [N, H, W] luma tensor (uint8 / uint16, may be a
     pitched view).  Returns two float64 device tensors [N]; ti[0] is NaN when

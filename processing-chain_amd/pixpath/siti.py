@@ -81,9 +81,20 @@ def siti_of_file(videofile, batch=120, reader=None, normalize=False, with_depth=
     """Per-frame SI/TI of a file: decoded luma only (pixpath.io.LumaReader:
     y4m/raw seek past chroma, ffmpeg decodes to gray/gray10le), streamed
     through pinned double buffers (siti_stream).  ``reader``: a full-frame
-    pixpath.io reader instead (its luma plane is used).  Returns (si, ti) or,
-    with_depth, (si, ti, bitdepth)."""
-    from . import io as pio
+    pixpath.io reader instead (its luma plane is used).  A v210 or UYVY AVI
+    needs no decoder: its packets go to the GPU as they are
+    (pixpath.io.PackedAviReader) and the luma is unpacked there
+    (siti_stream_packed; bitdepth 10 / 8).  Returns (si, ti) or, with_depth,
+    (si, ti, bitdepth)."""
+    from . import avi, io as pio
+    if reader is None and isinstance(videofile, str) and videofile.lower().endswith(".avi") \
+            and pio.packed_fourcc(avi.scan(videofile, headers_only=True)[0].get("fourcc")):
+        prd = pio.PackedAviReader(videofile)
+        try:
+            si, ti = siti_stream_packed(prd, batch=batch, normalize=normalize)
+        finally:
+            prd.close()
+        return (si, ti, prd.fmt.depth) if with_depth else (si, ti)
     if reader is not None:
         rd = _LumaOf(reader)
     else:
@@ -93,6 +104,42 @@ def siti_of_file(videofile, batch=120, reader=None, normalize=False, with_depth=
     finally:
         rd.close()
     return (si, ti, rd.depth) if with_depth else (si, ti)
+
+
+def siti_stream_packed(rd, batch=120, normalize=False, device=None):
+    """SI/TI of every frame of a packed reader (pixpath.io.PackedAviReader):
+    packets -> pinned buffer -> H2D as they are (a v210 frame is 2/3 the bytes
+    of its planar form) -> ops.unpack(luma_only=True) -> ops.siti, the last
+    luma frame of a batch staying resident as the next batch's TI halo."""
+    import torch
+
+    from . import ops
+    dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+    B, depth = int(batch), rd.fmt.depth
+    h_in = [torch.empty((B, rd.frame_bytes), dtype=torch.uint8).pin_memory() for _ in range(2)]
+    done = [None, None]  # H2D of the batch last read into each pinned buffer
+    outs, prev, k = [], None, 0
+    with torch.cuda.device(dev):
+        while True:
+            slot = k % 2
+            if done[slot] is not None:
+                done[slot].synchronize()
+            n = rd.read_into(h_in[slot].numpy(), B)
+            if n == 0:
+                break
+            d = h_in[slot][:n].to(dev, non_blocking=True)
+            done[slot] = torch.cuda.Event()
+            done[slot].record()
+            luma = ops.unpack(rd.device_batch(d), luma_only=True)
+            outs.append(ops.siti(luma, depth, prev=prev, normalize=normalize))
+            prev = luma[n - 1]
+            k += 1
+            if n < B:
+                break
+        torch.cuda.current_stream(dev).synchronize()
+    if not outs:
+        return np.zeros(0), np.zeros(0)
+    return (torch.cat([o[0] for o in outs]).cpu().numpy(), torch.cat([o[1] for o in outs]).cpu().numpy())
 
 
 class _LumaOf:

@@ -27,14 +27,14 @@ for f in ["/tmp/strip_u16.s", "/tmp/strip_u16_chain.s", "/tmp/strip_u8.s", "/tmp
 print("instances with VGPR spills:", bad)
 PY
 # every kernel of every HIP source: no private (scratch) segment
-for f in scale cpvs pack siti metrics; do
+for f in scale cpvs pack unpack siti metrics; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -x hip csrc/$f.hip --cuda-device-only -S -o /tmp/$f.s 2>/dev/null &
 done
 wait
 python3 - <<'PY'
 import re
 bad = []
-for f in ["scale", "cpvs", "pack", "siti", "metrics", "strip_u16", "strip_u16_chain", "strip_u8", "strip_u8_chain", "strip_u16_fused", "strip_u8_fused"]:
+for f in ["scale", "cpvs", "pack", "unpack", "siti", "metrics", "strip_u16", "strip_u16_chain", "strip_u8", "strip_u8_chain", "strip_u16_fused", "strip_u8_fused"]:
     txt = open('/tmp/%s.s' % f).read()
     for b in txt.split('  - .agpr_count:')[1:]:
         name = re.search(r"\.name:\s+(\S+)", b).group(1)
@@ -47,7 +47,7 @@ print("kernels with a private segment:", len(bad))
 PY
 # v_ashr_pk_u8_i32 keeps its destination's high half: a kernel that ORs more bytes
 # into such a result is wrong (cpvs.hip hit this); flag every occurrence
-if grep -l "v_ashr_pk_u8_i32" /tmp/scale.s /tmp/cpvs.s /tmp/pack.s /tmp/siti.s /tmp/strip_u16.s /tmp/strip_u16_chain.s /tmp/strip_u8.s /tmp/strip_u8_chain.s /tmp/strip_u16_fused.s /tmp/strip_u8_fused.s; then
+if grep -l "v_ashr_pk_u8_i32" /tmp/scale.s /tmp/cpvs.s /tmp/pack.s /tmp/unpack.s /tmp/siti.s /tmp/strip_u16.s /tmp/strip_u16_chain.s /tmp/strip_u8.s /tmp/strip_u8_chain.s /tmp/strip_u16_fused.s /tmp/strip_u8_fused.s; then
   echo "v_ashr_pk_u8_i32 present: check its uses"; exit 1
 fi
 echo "no v_ashr_pk_u8_i32"
