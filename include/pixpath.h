@@ -360,6 +360,30 @@ int pp_metrics(pp_ctx *ctx, int fmt, int w, int h, const pp_frames *ref,
                const pp_frames *dist, const int32_t *ref_index, int nframes,
                uint64_t *sse, double *ssim, void *stream);
 
+/* ---- per-frame Adler-32 (spec PP-HASH-1) -------------------
+ * The checksum FFmpeg's framecrc muxer prints for a frame, computed where the
+ * frame lies: 4 bytes a frame leave the device.  src: nframes w x h frames of
+ * any of the eight formats.  The byte string of a frame: planar formats plane
+ * 0, 1, 2, each row by row, the first width * bytes_per_sample bytes of every
+ * row exactly as stored (10-bit samples as their two little-endian bytes,
+ * nothing masked); uyvy422 the 2 w bytes of every row of plane 0; v210 the
+ * pp_v210_linesize(w) bytes of every row of plane 0 (the packet v210enc
+ * writes, zero fill included).  Bytes between a row's extent and its linesize
+ * never count.  out: DEVICE array of nframes uint32: Adler-32 of the string
+ * continued from `init` (low half a0, high half b0; 1 is zlib's default, 0
+ * framecrc's), i.e. zlib's adler32(init, bytes, N).  Exact for every size
+ * the call accepts.  An odd w of a packed format, a linesize below the row's
+ * bytes (v210: below pp_v210_linesize(w)), nframes < 0, w or h < 1 and NULL
+ * ctx, src, out or plane pointers are PP_ERR_INVALID; rows of 2^24 bytes or
+ * more and planes past the 2 GiB buffer range are PP_ERR_UNSUPPORTED.
+ * Arguments are checked before any HIP call; nframes == 0 is PP_OK.  Sources
+ * on the 16-byte grid (pointers, linesizes, frame strides) are read as 16-byte
+ * loads, anything else byte by byte with identical results.  The partials
+ * workspace belongs to the context.  Parity with FFmpeg's framecrc is
+ * unpinned.  Added without raising PP_ABI_VERSION (still 7). */
+int pp_frame_adler32(pp_ctx *ctx, int fmt, int w, int h, const pp_frames *src,
+                     int nframes, uint32_t init, uint32_t *out, void *stream);
+
 /* ---- host helpers --------------------------------------------------------
  * vf_fps output->input frame map (lib/ffmpeg.py:832-834, :959-961, :1038,
  * :1179): map[k] = input frame shown at output frame k.  Returns the number of

@@ -112,6 +112,9 @@ struct Ctx {
     // pp_metrics partials (PP-METRIC-1), grown on demand
     void *met_buf = nullptr;
     size_t met_cap = 0;
+    // pp_frame_adler32 partials (PP-HASH-1), grown on demand
+    void *crc_buf = nullptr;
+    size_t crc_cap = 0;
 };
 
 } // namespace pp

@@ -15,6 +15,8 @@ the ffmpeg strings they replace).
   siti   P.910 SI/TI of a SRC (util/SRC_analysis.py hook)
   metrics per-frame PSNR / SSIM of a PVS against its SRC (spec PP-METRIC-1; after p03);
           --crop WxH [--avpvs-pix-fmt NAME] scores a v210 / UYVY CPVS against its AVPVS
+  framecrc FFmpeg's `-f framecrc` listing of a file: one GPU Adler-32 per frame (spec PP-HASH-1);
+          --against FILE compares with a listing; `avpvs --framecrc FILE` lists what the writer was given
 
 Inputs/outputs ending in .y4m or .raw/.yuv are read/written directly;
 anything else goes through ffmpeg pipes.  The device is PIXPATH_DEVICE, else
@@ -165,6 +167,9 @@ def cmd_avpvs(args):
     else:
         inner = _open_writer(out, target, W, H, rate, args.vopts, args.aopts,
                              None if args.aopts.strip() == "-an" else args.input, args.y)
+    if args.framecrc:  # PP-HASH-1 of every frame handed to the AVPVS writer, listed on close
+        from .framecrc import FrameCrcWriter
+        inner = FrameCrcWriter(inner, args.framecrc, target, W, H, rate)
     stall = None
     if args.stall_output and not args.gpu_ffv1:
         # create_avpvs_short of a PVS with stalls: compose the stalled AVPVS
@@ -653,6 +658,26 @@ def cmd_metrics(args):
     return 0
 
 
+def cmd_framecrc(args):
+    """FFmpeg's `-f framecrc` listing of a file (spec PP-HASH-1), or with
+    --against the comparison with a listing: one JSON line, exit status 1 on a
+    difference."""
+    from . import framecrc
+    res = framecrc.checksums_of_file(args.input, batch=args.batch, seed=args.seed, packets=args.packets)
+    text = framecrc.format_lines(res["frames"], res["w"], res["h"], res["rate"])
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text)
+    if args.against:
+        with open(args.against) as f:
+            diff = framecrc.compare(res["frames"], framecrc.parse(f.read()))
+        print(json.dumps(framecrc.report(len(res["frames"]), diff)))
+        return 0 if diff is None else 1
+    if not args.out:
+        sys.stdout.write(text)
+    return 0
+
+
 def _avi(path):
     return str(path).lower().endswith(".avi")
 
@@ -690,6 +715,8 @@ def main(argv=None):
     p.add_argument("--gpu-ffv1", action="store_true", help="FFV1 encoded on the GPU into an AVI (pixpath.avi)")
     p.add_argument("--ffv1-slices", default=None, help="slice grid HxV of the GPU FFV1 (default PIXPATH_FFV1_SLICES, 8x8)")
     p.add_argument("--ffv1-input", action="store_true", help="input is a --gpu-ffv1 AVI: decode it on the GPU")
+    p.add_argument("--framecrc", default=None, metavar="FILE",
+                   help="write the framecrc listing (spec PP-HASH-1) of the frames handed to the writer")
     p.set_defaults(fn=cmd_avpvs)
 
     p = sub.add_parser("encseg")
@@ -756,6 +783,17 @@ def main(argv=None):
     p.add_argument("--avpvs-pix-fmt", default=None, metavar="NAME",
                    help="pixel format of the AVPVS the CPVS was padded from (yuv420p...: rows offset rounded to even)")
     p.set_defaults(fn=cmd_metrics)
+
+    p = sub.add_parser("framecrc")
+    p.add_argument("input", metavar="INPUT")
+    p.add_argument("--seed", type=lambda v: int(v, 0), default=0,
+                   help="start value of every frame's Adler-32 (0: FFmpeg's framecrc; 1: zlib's default)")
+    p.add_argument("--packets", action="store_true",
+                   help="a v210 AVI: hash the packed payload (`-c copy`), not the decoded yuv422p10le")
+    p.add_argument("--out", default=None, metavar="FILE", help="write the listing here instead of printing it")
+    p.add_argument("--against", default=None, metavar="FILE", help="compare with this framecrc listing")
+    p.add_argument("--batch", type=int, default=32)
+    p.set_defaults(fn=cmd_framecrc)
 
     args = ap.parse_args(argv)
     # GPU FFV1 applies to AVI files (the reference's AVPVS container); Y4M /

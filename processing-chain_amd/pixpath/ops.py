@@ -309,6 +309,36 @@ def metrics(ref, dist, ref_index=None, stream=None):
     return sse, ssim
 
 
+# frame_adler32 kernel geometry (csrc/framecrc.hip), for tests that place sizes on its seams
+CRC_LANE_BYTES = 16   # kCrcLaneBytes: bytes a lane loads per piece
+CRC_LANES = 64        # kCrcLanes: a wave covers CRC_LANES * CRC_LANE_BYTES bytes of a row per trip
+CRC_WAVE_ROWS = 16    # kCrcWaveRows: rows of a band one wave sums
+CRC_BAND_ROWS = 64    # kCrcBandRows: rows of a unit (4 waves)
+
+
+def frame_adler32(batch, init=0, stream=None):
+    """Per-frame Adler-32 of a FrameBatch of any of the eight formats (spec
+    PP-HASH-1, pp_frame_adler32): zlib.adler32 of each frame's byte string
+    (planes in order, row by row without the pitch padding; packed formats the
+    rows of plane 0) continued from ``init`` -- 0 is what FFmpeg's framecrc
+    starts from, 1 zlib's default.  Returns a device tensor [N] of dtype
+    torch.uint32 (the kernel's own output, no conversion pass): ``.cpu()``,
+    ``.tolist()``, ``.numpy()`` and indexing give the unsigned values; torch
+    implements little arithmetic for this dtype, so compare and combine on the
+    host."""
+    n = batch.n
+    dev = batch.device
+    if n == 0:  # an empty batch has no plane pointers to pass
+        return torch.empty(0, dtype=torch.uint32, device=dev)
+    out = torch.empty(n, dtype=torch.uint32, device=dev)
+    ctx = context(dev.index)
+    s = batch.frames_struct()
+    check(lib().pp_frame_adler32(ctx.handle, batch.fmt.id, batch.w, batch.h, ctypes.byref(s), n,
+                                 ctypes.c_uint32(int(init) & 0xffffffff), ctypes.c_void_p(out.data_ptr()),
+                                 _stream(batch.planes[0], stream)))
+    return out
+
+
 def spinner_upload(rgba_frames, f, device=None):
     """Upload an RGBA8 animation [n, h, w, 4] (host) for stall compositing."""
     a = np.ascontiguousarray(rgba_frames, dtype=np.uint8)
