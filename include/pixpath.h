@@ -384,6 +384,41 @@ int pp_metrics(pp_ctx *ctx, int fmt, int w, int h, const pp_frames *ref,
 int pp_frame_adler32(pp_ctx *ctx, int fmt, int w, int h, const pp_frames *src,
                      int nframes, uint32_t init, uint32_t *out, void *stream);
 
+/* ---- per-frame signal statistics (spec PP-STATS-1) ----------
+ * What is inside a clip: per frame and plane the histogram of the samples and
+ * the sum of absolute differences to the previous frame, in one pass over the
+ * frames where they lie.  src: nframes w x h frames of one of the six planar
+ * formats (a packed format is PP_ERR_INVALID: unpack it first with
+ * pp_unpack_execute).  Plane sizes follow pp_plane_bytes' rule (a chroma plane
+ * is (w+1)>>hsub by (h+1)>>vsub); only the first width samples of a row count,
+ * pitch padding never does.  Three DEVICE arrays, frame-major, each written in
+ * full (the caller need not clear them):
+ *   hist [nframes][3][bins] uint32, bins = 1 << depth (256 or 1024):
+ *        hist[k][p][v] = samples of plane p of frame k equal to v; a stored
+ *        16-bit sample >= 1024 of a 10-bit format is in no bin;
+ *   over [nframes][3] uint32: the 10-bit samples >= 1024 (0 for 8-bit
+ *        formats); sum(hist[k][p]) + over[k][p] == samples of the plane;
+ *   sad  [nframes][3] uint64: sum over the plane of |src[k] - src[k-1]| on the
+ *        samples as stored (the raw 16-bit value, nothing masked).  Frame 0 is
+ *        compared with `prev`, a one-frame batch of the same fmt, w and h with
+ *        pitches of its own; without prev (NULL) sad[0][p] = UINT64_MAX:
+ *        absent, as pp_siti's NaN ti[0].  sad == NULL skips the differences
+ *        (prev is then ignored).
+ * All three are exact integers and identical from run to run.  NULL ctx, src,
+ * hist, over or plane pointers, w or h < 1, nframes < 0 and a linesize below
+ * the row's bytes are PP_ERR_INVALID; a plane of 2^31 samples or more (a bin
+ * is 32 bits) or past the 2 GiB buffer range is PP_ERR_UNSUPPORTED.  Arguments
+ * are checked before any HIP call; nframes == 0 is PP_OK and writes nothing.
+ * Sources on the 16-byte grid (pointers, linesizes, frame strides, prev's too)
+ * are read as 16-byte loads, anything else byte by byte with identical
+ * results.  The workspace (one histogram per frame and 64-row x 1024-byte
+ * tile) belongs to the context.  Parity of the derived values with FFmpeg's
+ * signalstats / blackdetect / freezedetect is unpinned.  Added without raising
+ * PP_ABI_VERSION (still 7). */
+int pp_frame_stats(pp_ctx *ctx, int fmt, int w, int h, const pp_frames *src,
+                   int nframes, const pp_frames *prev,
+                   uint32_t *hist, uint64_t *sad, uint32_t *over, void *stream);
+
 /* ---- host helpers --------------------------------------------------------
  * vf_fps output->input frame map (lib/ffmpeg.py:832-834, :959-961, :1038,
  * :1179): map[k] = input frame shown at output frame k.  Returns the number of

@@ -40,11 +40,12 @@ extern "C" int pp_ctx_create(int device, pp_ctx **out) {
 
 extern "C" int pp_ctx_destroy(pp_ctx *ctx) {
     if (!ctx) return PP_OK;
-    if (ctx->spin_buf || ctx->met_buf || ctx->crc_buf) {
+    if (ctx->spin_buf || ctx->met_buf || ctx->crc_buf || ctx->stat_buf) {
         (void)hipSetDevice(ctx->device);
         if (ctx->spin_buf) (void)hipFree(ctx->spin_buf);
         if (ctx->met_buf) (void)hipFree(ctx->met_buf);
         if (ctx->crc_buf) (void)hipFree(ctx->crc_buf);
+        if (ctx->stat_buf) (void)hipFree(ctx->stat_buf);
     }
     delete ctx;
     return PP_OK;

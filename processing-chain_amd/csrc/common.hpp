@@ -115,6 +115,9 @@ struct Ctx {
     // pp_frame_adler32 partials (PP-HASH-1), grown on demand
     void *crc_buf = nullptr;
     size_t crc_cap = 0;
+    // pp_frame_stats tile histograms (PP-STATS-1), grown on demand
+    void *stat_buf = nullptr;
+    size_t stat_cap = 0;
 };
 
 } // namespace pp

@@ -17,6 +17,8 @@ the ffmpeg strings they replace).
           --crop WxH [--avpvs-pix-fmt NAME] scores a v210 / UYVY CPVS against its AVPVS
   framecrc FFmpeg's `-f framecrc` listing of a file: one GPU Adler-32 per frame (spec PP-HASH-1);
           --against FILE compares with a listing; `avpvs --framecrc FILE` lists what the writer was given
+  stats  what is inside one clip (spec PP-STATS-1): per-plane range, mean, percentiles, used bits,
+          out-of-range and out-of-container samples, black and repeated frames, from one GPU pass
 
 Inputs/outputs ending in .y4m or .raw/.yuv are read/written directly;
 anything else goes through ffmpeg pipes.  The device is PIXPATH_DEVICE, else
@@ -678,6 +680,23 @@ def cmd_framecrc(args):
     return 0
 
 
+def cmd_stats(args):
+    """Per-frame signal statistics of a file (spec PP-STATS-1): one JSON line."""
+    from . import stats
+    kw = {}
+    if args.crop:  # a CPVS canvas: analyse the AVPVS picture inside it
+        cw, ch = args.crop.lower().split("x")
+        kw["crop"] = (int(cw), int(ch))
+        if args.avpvs_pix_fmt:
+            kw["crop_from"] = args.avpvs_pix_fmt
+    elif args.avpvs_pix_fmt:
+        raise SystemExit("--avpvs-pix-fmt needs --crop")
+    res = stats.stats_of_file(args.input, batch=args.batch, pix_th=args.black_pix_th, pic_th=args.black_pic_th,
+                              histogram=args.histogram, **kw)
+    print(json.dumps(stats.report(res, args.input, per_frame=args.per_frame)))
+    return 0
+
+
 def _avi(path):
     return str(path).lower().endswith(".avi")
 
@@ -794,6 +813,21 @@ def main(argv=None):
     p.add_argument("--against", default=None, metavar="FILE", help="compare with this framecrc listing")
     p.add_argument("--batch", type=int, default=32)
     p.set_defaults(fn=cmd_framecrc)
+
+    p = sub.add_parser("stats")
+    p.add_argument("input", metavar="INPUT")
+    p.add_argument("--per-frame", action="store_true")
+    p.add_argument("--histogram", action="store_true", help="add the clip's per-plane histograms")
+    p.add_argument("--crop", default=None, metavar="WxH",
+                   help="the input is a v210 / UYVY CPVS: analyse the WxH AVPVS picture inside its canvas")
+    p.add_argument("--avpvs-pix-fmt", default=None, metavar="NAME",
+                   help="pixel format of the AVPVS the CPVS was padded from (yuv420p...: rows offset rounded to even)")
+    p.add_argument("--black-pix-th", type=float, default=0.10,
+                   help="a luma sample is black up to 16 + this share of the limited range (blackdetect's pix_th)")
+    p.add_argument("--black-pic-th", type=float, default=0.98,
+                   help="a frame is black from this share of black luma samples (blackdetect's pic_th)")
+    p.add_argument("--batch", type=int, default=32)
+    p.set_defaults(fn=cmd_stats)
 
     args = ap.parse_args(argv)
     # GPU FFV1 applies to AVI files (the reference's AVPVS container); Y4M /

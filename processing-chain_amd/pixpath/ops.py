@@ -339,6 +339,42 @@ def frame_adler32(batch, init=0, stream=None):
     return out
 
 
+def frame_stats(batch, prev=None, want_sad=True, stream=None):
+    """Per-frame, per-plane histogram, difference sum and out-of-container
+    count of a planar FrameBatch (spec PP-STATS-1, pp_frame_stats).  Returns
+    device tensors on the current stream: ``hist`` int32 [N, 3, bins]
+    (bins = 1 << depth; a bin stays below 2^31), ``sad`` int64 [N, 3] (the sum
+    of |frame k - frame k-1| per plane, below 2^47; frame 0 against ``prev``,
+    a one-frame batch of the same format and size, or without it -1 = absent:
+    the kernel's UINT64_MAX read as int64; None with ``want_sad`` False, which
+    skips the differences) and ``over`` int32 [N, 3] (10-bit samples >= 1024,
+    in no bin).  pixpath.stats.summarize turns the three into the reported
+    values."""
+    if batch.fmt.packed:
+        raise ValueError("frame_stats takes a planar batch: unpack %s first (ops.unpack)" % batch.fmt.name)
+    n, dev = batch.n, batch.device
+    bins = 1 << batch.fmt.depth
+    hist = torch.empty((n, 3, bins), dtype=torch.int32, device=dev)
+    over = torch.empty((n, 3), dtype=torch.int32, device=dev)
+    sad = torch.empty((n, 3), dtype=torch.int64, device=dev) if want_sad else None
+    if n == 0:  # an empty batch has no plane pointers to pass
+        return hist, sad, over
+    pp = None
+    if prev is not None and want_sad:
+        if (prev.fmt.id, prev.w, prev.h) != (batch.fmt.id, batch.w, batch.h) or prev.n < 1:
+            raise ValueError("prev must be one frame of the batch's format and size")
+        if prev.device != dev:
+            raise ValueError("prev is on another device")
+        ps = prev.frames_struct()
+        pp = ctypes.byref(ps)
+    ctx = context(dev.index)
+    s = batch.frames_struct()
+    check(lib().pp_frame_stats(ctx.handle, batch.fmt.id, batch.w, batch.h, ctypes.byref(s), n, pp,
+                               ctypes.c_void_p(hist.data_ptr()), None if sad is None else ctypes.c_void_p(sad.data_ptr()),
+                               ctypes.c_void_p(over.data_ptr()), _stream(batch.planes[0], stream)))
+    return hist, sad, over
+
+
 def spinner_upload(rgba_frames, f, device=None):
     """Upload an RGBA8 animation [n, h, w, 4] (host) for stall compositing."""
     a = np.ascontiguousarray(rgba_frames, dtype=np.uint8)
