@@ -40,12 +40,13 @@ extern "C" int pp_ctx_create(int device, pp_ctx **out) {
 
 extern "C" int pp_ctx_destroy(pp_ctx *ctx) {
     if (!ctx) return PP_OK;
-    if (ctx->spin_buf || ctx->met_buf || ctx->crc_buf || ctx->stat_buf) {
-        (void)hipSetDevice(ctx->device);
-        if (ctx->spin_buf) (void)hipFree(ctx->spin_buf);
-        if (ctx->met_buf) (void)hipFree(ctx->met_buf);
-        if (ctx->crc_buf) (void)hipFree(ctx->crc_buf);
-        if (ctx->stat_buf) (void)hipFree(ctx->stat_buf);
+    void *const bufs[] = {ctx->spin_buf, ctx->met.buf, ctx->crc.buf, ctx->stat.buf};
+    bool set = false;  // the device is touched only if there is something to free
+    for (void *b : bufs) {
+        if (!b) continue;
+        if (!set) (void)hipSetDevice(ctx->device);
+        set = true;
+        (void)hipFree(b);
     }
     delete ctx;
     return PP_OK;

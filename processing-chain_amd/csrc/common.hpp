@@ -103,21 +103,22 @@ inline int xcd_remap(int b, int n) {
     return k < rem ? k * (per + 1) + q : rem * (per + 1) + (k - rem) * per + q;
 }
 
+// A device buffer grown on demand (grow, analysis_host.hpp) and kept by the context.
+struct Scratch {
+    void *buf = nullptr;
+    size_t cap = 0;
+};
+
 struct Ctx {
     int device = 0;
     int cus = 0;  // compute units (persistent grids)
     // spinner animation (PP-STALL-1), device resident
     int spin_fmt = -1, spin_n = 0, spin_w = 0, spin_h = 0;
     void *spin_buf = nullptr; // [n][Y(w*h) A(w*h) U V Ac (cw*ch each)] uint16
-    // pp_metrics partials (PP-METRIC-1), grown on demand
-    void *met_buf = nullptr;
-    size_t met_cap = 0;
-    // pp_frame_adler32 partials (PP-HASH-1), grown on demand
-    void *crc_buf = nullptr;
-    size_t crc_cap = 0;
-    // pp_frame_stats tile histograms (PP-STATS-1), grown on demand
-    void *stat_buf = nullptr;
-    size_t stat_cap = 0;
+    // partials of pp_metrics (PP-METRIC-1) and pp_frame_adler32 (PP-HASH-1), tile
+    // histograms of pp_frame_stats (PP-STATS-1).  One each: the three may be
+    // enqueued on different streams at once.
+    Scratch met, crc, stat;
 };
 
 } // namespace pp

@@ -46,13 +46,13 @@
 // addition mod M is order-independent anyway).
 //
 // Pointers, linesizes or frame strides off the 16-B grid: the same kernel with
-// byte loads and explicit bounds (ALIGNED = false), equal results.
+// byte loads and explicit bounds (ALIGNED = false), equal results.  The piece
+// loader, its mask, the descriptor and the butterfly: analysis_dev.hpp.
 #include <algorithm>
 #include <cstdlib>
 
-#include "common.hpp"
-#include "device.hpp"
-#include "pack_plan.hpp"
+#include "analysis_dev.hpp"
+#include "analysis_host.hpp"
 
 namespace pp {
 
@@ -83,7 +83,7 @@ struct CrcArgs {
 template <bool ALIGNED, bool RAGGED>
 __device__ __forceinline__ void crc_unit(const CrcArgs &a, int k, int tile, CrcPartial *out) {
     __shared__ uint32_t s_a[kCrcWaves], s_b[kCrcWaves];
-    const int p = tile >= a.tile0[2] ? 2 : tile >= a.tile0[1] ? 1 : 0;
+    const int p = plane_of_tile(a.tile0, tile);
     const int band = tile - a.tile0[p];
     const int rb = a.rb[p], ph = a.ph[p], trips = a.trips[p];
     const int lane = threadIdx.x & 63;
@@ -91,11 +91,7 @@ __device__ __forceinline__ void crc_unit(const CrcArgs &a, int k, int tile, CrcP
     const int r0 = band * kCrcBandRows + wave * kCrcWaveRows;  // the wave's first row
     const int n = min(max(ph - r0, 0), kCrcWaveRows);          // and how many it has
     const uint8_t *base = a.data[p] + (int64_t)k * a.fs[p];
-    const uint32_t ls = (uint32_t)a.ls[p];
-    // a load straddling num_records reads 0 as a whole: the last row counts up
-    // to its 16-B-rounded extent, which lies inside the (aligned) pitch
-    const int64_t wb = ((int64_t)rb + 15) & ~int64_t(15);
-    const auto rs = uniform_rsrc(base, ALIGNED ? (int)((int64_t)(ph - 1) * a.ls[p] + wb) : 0);
+    const auto rs = plane_rsrc<ALIGNED>(base, ph, a.ls[p], rb);
 
     uint32_t A = 0;
     int64_t B = 0;
@@ -110,52 +106,25 @@ __device__ __forceinline__ void crc_unit(const CrcArgs &a, int k, int tile, CrcP
             const bool in = i + u < total && c < rb;
             nv[u] = in ? rb - c : 0;  // bytes of the piece inside the row (may exceed 16)
             wgt[u] = (n - 1 - r) * rb + rb - c - kCrcLaneBytes;
-            if constexpr (ALIGNED) {
-                const uint32_t voff = in ? (uint32_t)(r0 + r) * ls + (uint32_t)c : (uint32_t)kOobOff;
-                const auto v = __builtin_amdgcn_raw_buffer_load_b128(rs, voff, 0, 0);
-                __builtin_memcpy(q[u], &v, 16);
-            } else {
-                // every load goes to a byte of the row (clamped); the select drops the others
-                const uint8_t *row = base + (int64_t)(r0 + min(r, n - 1)) * a.ls[p];
-#pragma unroll
-                for (int d = 0; d < 4; ++d) {
-                    uint32_t v = 0;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const int x = c + 4 * d + e;
-                        const uint32_t s = row[min(x, rb - 1)];
-                        v |= ((in && x < rb) ? s : 0u) << (8 * e);
-                    }
-                    q[u][d] = v;
-                }
-            }
+            load_piece<uint8_t, ALIGNED>(q[u], rs, base, a.ls[p], r0 + r, ph, c, rb, in);
             if (++t == trips) { t = 0; ++r; }
         }
 #pragma unroll
         for (int u = 0; u < kCrcGroup; ++u) {
             uint32_t s1 = 0, s2 = 0;
+            if constexpr (RAGGED && ALIGNED) mask_piece(q[u], nv[u]);
 #pragma unroll
             for (int d = 0; d < 4; ++d) {
-                uint32_t v = q[u][d];
-                if constexpr (RAGGED && ALIGNED) {
-                    const int nb = nv[u] - 4 * d;  // bytes of this dword inside the row
-                    v &= nb >= 4 ? 0xffffffffu : nb <= 0 ? 0u : (1u << (8 * nb)) - 1u;
-                }
                 // byte j of the piece weighs 16 - j; byte 0 is the low byte of dword 0
-                s1 = __builtin_amdgcn_udot4(v, 0x01010101u, s1, false);
-                s2 = __builtin_amdgcn_udot4(v, 0x0D0E0F10u - 0x04040404u * d, s2, false);
+                s1 = __builtin_amdgcn_udot4(q[u][d], 0x01010101u, s1, false);
+                s2 = __builtin_amdgcn_udot4(q[u][d], 0x0D0E0F10u - 0x04040404u * d, s2, false);
             }
             A += s1;
             B += (int64_t)wgt[u] * (int64_t)(int32_t)s1 + (int64_t)s2;
         }
     }
 
-    uint32_t ra = A % kAdlerMod, rbm = (uint32_t)((uint64_t)B % kAdlerMod);
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        ra += __shfl_xor(ra, o, 64);
-        rbm += __shfl_xor(rbm, o, 64);
-    }
+    const uint32_t ra = wave_sum(A % kAdlerMod), rbm = wave_sum((uint32_t)((uint64_t)B % kAdlerMod));
     __syncthreads();  // the previous unit's partial has been read
     if (lane == 0) { s_a[wave] = ra % kAdlerMod; s_b[wave] = rbm % kAdlerMod; }
     __syncthreads();
@@ -198,19 +167,14 @@ __global__ __launch_bounds__(64) void crc_finalize(const CrcPartial *part, CrcFi
     const CrcPartial *q = part + k * f.tiles;
     uint64_t sa = 0, sb = 0;
     for (int t = threadIdx.x; t < f.tiles; t += 64) {
-        const int p = t >= f.tile0[2] ? 2 : t >= f.tile0[1] ? 1 : 0;
+        const int p = plane_of_tile(f.tile0, t);
         const int rows_end = min((t - f.tile0[p] + 1) * kCrcBandRows, f.ph[p]);
         const int64_t rest = f.N - (f.off[p] + (int64_t)rows_end * f.rb[p]);
         const CrcPartial v = q[t];
         sa += v.a;
         sb += v.b + (uint64_t)((uint32_t)(rest % kAdlerMod) * v.a);
     }
-    uint32_t ra = (uint32_t)(sa % kAdlerMod), rbm = (uint32_t)(sb % kAdlerMod);
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        ra += __shfl_xor(ra, o, 64);
-        rbm += __shfl_xor(rbm, o, 64);
-    }
+    const uint32_t ra = wave_sum((uint32_t)(sa % kAdlerMod)), rbm = wave_sum((uint32_t)(sb % kAdlerMod));
     if (threadIdx.x == 0) {
         const uint32_t a0 = init & 0xffffu, b0 = init >> 16;
         const uint32_t A = (a0 + ra) % kAdlerMod;
@@ -233,26 +197,20 @@ extern "C" int pp_frame_adler32(pp_ctx *ctx, int fmt, int w, int h, const pp_fra
         PP_FAIL(PP_ERR_INVALID, "%s needs an even width, not %d", fmt == PP_FMT_V210 ? "v210" : "uyvy422", w);
     if (nframes < 0) PP_FAIL(PP_ERR_INVALID, "nframes %d < 0", nframes);
     const int npl = fi.packed ? 1 : 3;
-    const int es = !fi.packed && fi.depth > 8 ? 2 : 1;
     CrcArgs a{};
     CrcFinal f{};
     bool aligned = true, ragged = false;
     for (int p = 0; p < 3; ++p) {
         a.tile0[p] = f.tile0[p] = a.tiles;
         if (p >= npl) continue;  // no units: tile0 = tiles keeps every unit in the planes before
-        const int pw = p ? ceil_rshift(w, fi.hsub) : w, ph = p ? ceil_rshift(h, fi.vsub) : h;
-        const int64_t rb = fmt == PP_FMT_V210 ? v210_linesize(w) : fmt == PP_FMT_UYVY422 ? 2LL * w : (int64_t)pw * es;
-        const int64_t ls = src->linesize[p], fs = src->frame_stride[p];
-        if (!src->data[p]) PP_FAIL(PP_ERR_INVALID, "plane %d: null data", p);
-        if (ls < rb) PP_FAIL(PP_ERR_INVALID, "plane %d: linesize %lld below the row's %lld bytes", p, (long long)ls, (long long)rb);
+        PlaneGeom g = plane_geom(fmt, w, h, p);
+        const int64_t rb = g.rb;
+        const int ph = g.ph;
+        if (int e = check_plane(src, p, g, aligned)) return e;
         if (rb >= kCrcMaxRow) PP_FAIL(PP_ERR_UNSUPPORTED, "plane %d: rows of %lld bytes (limit %lld)", p, (long long)rb, (long long)kCrcMaxRow);
-        // lane offsets stay inside the 31-bit buffer range
-        if ((int64_t)ph * ls >= (int64_t)kOobOff)
-            PP_FAIL(PP_ERR_UNSUPPORTED, "plane %d of %lld bytes exceeds the 2 GiB buffer range", p, (long long)(ph * ls));
-        aligned &= !(((uintptr_t)src->data[p] | (uint64_t)ls | (uint64_t)fs) & 15);
         ragged |= (rb & 15) != 0;
         a.data[p] = static_cast<const uint8_t *>(src->data[p]);
-        a.ls[p] = ls; a.fs[p] = fs;
+        a.ls[p] = g.ls; a.fs[p] = g.fs;
         a.rb[p] = f.rb[p] = (int)rb; a.ph[p] = f.ph[p] = ph;
         a.trips[p] = (int)((rb + kCrcLanes * kCrcLaneBytes - 1) / (kCrcLanes * kCrcLaneBytes));
         a.tiles += (ph + kCrcBandRows - 1) / kCrcBandRows;
@@ -265,14 +223,8 @@ extern "C" int pp_frame_adler32(pp_ctx *ctx, int fmt, int w, int h, const pp_fra
     hipStream_t st = static_cast<hipStream_t>(stream);
     PP_HIP(hipSetDevice(ctx->device));
     a.total = (int64_t)nframes * a.tiles;
-    const size_t need = sizeof(CrcPartial) * (size_t)a.total;
-    if (need > ctx->crc_cap) {  // grown on demand, kept by the context (hipFree waits for earlier users)
-        if (ctx->crc_buf) PP_HIP(hipFree(ctx->crc_buf));
-        ctx->crc_buf = nullptr; ctx->crc_cap = 0;
-        PP_HIP(hipMalloc(&ctx->crc_buf, need));
-        ctx->crc_cap = need;
-    }
-    a.part = static_cast<CrcPartial *>(ctx->crc_buf);
+    if (int e = grow(ctx->crc, sizeof(CrcPartial) * (size_t)a.total)) return e;
+    a.part = static_cast<CrcPartial *>(ctx->crc.buf);
 
     using KFn = void (*)(const CrcArgs);
     const KFn k = !aligned ? crc_kernel<false, true> : ragged ? crc_kernel<true, true> : crc_kernel<true, false>;

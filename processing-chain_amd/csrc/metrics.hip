@@ -30,12 +30,15 @@
 // Reduction: lane -> wave (xor butterfly) -> workgroup (4 values through LDS
 // in wave order) -> one partial per unit, no atomics; metrics_finalize adds a
 // (frame, plane)'s partials in unit order: bit-reproducible.
+// The piece loader, the plane descriptor, the edge mask and the butterfly are
+// the analysis kernels' common ones (analysis_dev.hpp); the unaligned path
+// reads uint16_t samples there, so 10-bit planes may sit on the 2-byte grid.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
 
-#include "common.hpp"
-#include "device.hpp"
+#include "analysis_dev.hpp"
+#include "analysis_host.hpp"
 
 namespace pp {
 
@@ -77,39 +80,13 @@ struct Quad {
     uint32_t w[4][4];
 };
 
-// Rows r0..r0+3 of a plane at lane byte offset voff (kOob for a lane right of
-// the plane).  ALIGNED: one 16-B buffer load a row; rows >= ph lie past the
-// descriptor's range and read 0.  Otherwise sample by sample with explicit
-// bounds (pointers or pitches off the 16-B grid).
+// Rows r0..r0+3 of a plane at the lane's byte column c (load_piece; rows >= ph
+// read 0 through the descriptor's range or the clamp).
 template <typename T, bool ALIGNED>
-__device__ inline void load_quad(Quad &q, const uint8_t *base, __amdgpu_buffer_rsrc_t rs, uint32_t voff, uint32_t ls,
-                                 int r0, int x, int pw, int ph) {
-    if constexpr (ALIGNED) {
+__device__ inline void load_quad(Quad &q, __amdgpu_buffer_rsrc_t rs, const uint8_t *base, int64_t ls, int r0, int ph,
+                                 int c, int rb, bool in) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const auto v = __builtin_amdgcn_raw_buffer_load_b128(rs, voff + (uint32_t)(r0 + j) * ls, 0, 0);
-            __builtin_memcpy(q.w[j], &v, 16);
-        }
-    } else {
-        constexpr int SPD = 4 / sizeof(T);  // samples per dword
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            // every load goes to a sample of the plane (clamped); the select drops the others
-            const T *row = reinterpret_cast<const T *>(base + (int64_t)min(r0 + j, ph - 1) * ls);
-            const bool row_in = r0 + j < ph;
-#pragma unroll
-            for (int d = 0; d < 4; ++d) {
-                uint32_t v = 0;
-#pragma unroll
-                for (int e = 0; e < SPD; ++e) {
-                    const int xe = x + d * SPD + e;
-                    const uint32_t s = row[min(xe, pw - 1)];
-                    v |= ((row_in && xe < pw) ? s : 0u) << (8 * sizeof(T) * e);
-                }
-                q.w[j][d] = v;
-            }
-        }
-    }
+    for (int j = 0; j < 4; ++j) load_piece<T, ALIGNED>(q.w[j], rs, base, ls, r0 + j, ph, c, rb, in);
 }
 
 // One window from its exact sums; widened before multiplying (PP-METRIC-1).
@@ -128,12 +105,11 @@ __device__ __forceinline__ void metrics_unit(const MetArgs &a, int k, int tile, 
     constexpr int PX = kMetLaneBytes / sizeof(T);  // samples per lane and row
     constexpr int LB = PX / 4;                     // blocks per lane
     constexpr int DPB = 4 / LB;                    // dwords per block row of a block
-    constexpr int SPD = 4 / sizeof(T);
     constexpr uint32_t kOnes = sizeof(T) == 2 ? 0x00010001u : 0x01010101u;
     __shared__ uint64_t s_sse[kMetWaves];
     __shared__ double s_ssim[kMetWaves];
 
-    const int p = tile >= a.tile0[2] ? 2 : tile >= a.tile0[1] ? 1 : 0;
+    const int p = plane_of_tile(a.tile0, tile);
     const int t = tile - a.tile0[p];
     const int tx = t % a.tiles_x[p], band = t / a.tiles_x[p];
     const int pw = a.pw[p], ph = a.ph[p];
@@ -147,23 +123,17 @@ __device__ __forceinline__ void metrics_unit(const MetArgs &a, int k, int tile, 
     const int rf = a.identity ? k : a.idx[k];
     const uint8_t *rbase = a.ref[p] + (int64_t)rf * a.rfs[p];
     const uint8_t *dbase = a.dist[p] + (int64_t)k * a.dfs[p];
-    const uint32_t rls = (uint32_t)a.rls[p], dls = (uint32_t)a.dls[p];
-    // a row load straddling num_records reads 0 as a whole: the last row counts
-    // up to its 16-B-rounded width, which lies inside the (aligned) pitch
-    const int64_t wb = ((int64_t)pw * sizeof(T) + 15) & ~int64_t(15);
-    const auto rrs = uniform_rsrc(rbase, ALIGNED ? (int)((int64_t)(ph - 1) * a.rls[p] + min(a.rls[p], wb)) : 0);
-    const auto drs = uniform_rsrc(dbase, ALIGNED ? (int)((int64_t)(ph - 1) * a.dls[p] + min(a.dls[p], wb)) : 0);
-    const uint32_t voff = x < pw ? (uint32_t)(x * (int)sizeof(T)) : (uint32_t)kOobOff;
+    const int64_t rls = a.rls[p], dls = a.dls[p];
+    const int rb = pw * (int)sizeof(T), xb = x * (int)sizeof(T);  // bytes of a row; the lane's byte column
+    // ALIGNED: the column test is made once, here: a lane right of the plane has kOobOff as its
+    // column (row * ls + kOobOff < 2^32 by the range check) and load_piece's per-row select folds
+    const int c = ALIGNED && x >= pw ? kOobOff : xb;
+    const bool in = ALIGNED || x < pw;
+    const auto rrs = plane_rsrc<ALIGNED>(rbase, ph, rls, rb);
+    const auto drs = plane_rsrc<ALIGNED>(dbase, ph, dls, rb);
 
-    uint32_t mask[4];  // RAGGED: the samples of the lane inside the plane
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-        uint32_t m = 0;
-#pragma unroll
-        for (int e = 0; e < SPD; ++e)
-            if (x + d * SPD + e < pw) m |= (sizeof(T) == 2 ? 0xffffu : 0xffu) << (8 * sizeof(T) * e);
-        mask[d] = m;
-    }
+    uint32_t mask[4] = {~0u, ~0u, ~0u, ~0u};  // RAGGED: the samples of the lane inside the plane
+    mask_piece(mask, rb - xb);
     const double mx = (double)((1 << a.depth) - 1);
     const double c1 = .01 * .01 * mx * mx * 64.0, c2 = .03 * .03 * mx * mx * 64.0 * 63.0;
 
@@ -171,14 +141,14 @@ __device__ __forceinline__ void metrics_unit(const MetArgs &a, int k, int tile, 
     double acc = 0.0;
     uint32_t prev[LB][4];  // horizontal block pairs of the block row above
     Quad qa, qb;
-    load_quad<T, ALIGNED>(qa, rbase, rrs, voff, rls, 4 * b0, x, pw, ph);
-    load_quad<T, ALIGNED>(qb, dbase, drs, voff, dls, 4 * b0, x, pw, ph);
+    load_quad<T, ALIGNED>(qa, rrs, rbase, rls, 4 * b0, ph, c, rb, in);
+    load_quad<T, ALIGNED>(qb, drs, dbase, dls, 4 * b0, ph, c, rb, in);
     // block row i of the band (kBandBlocks is the halo block row)
     auto step = [&](int i) {
         Quad ca = qa, cb = qb;
         if (i < kBandBlocks) {  // the next block row travels while this one is summed
-            load_quad<T, ALIGNED>(qa, rbase, rrs, voff, rls, 4 * (b0 + i + 1), x, pw, ph);
-            load_quad<T, ALIGNED>(qb, dbase, drs, voff, dls, 4 * (b0 + i + 1), x, pw, ph);
+            load_quad<T, ALIGNED>(qa, rrs, rbase, rls, 4 * (b0 + i + 1), ph, c, rb, in);
+            load_quad<T, ALIGNED>(qb, drs, dbase, dls, 4 * (b0 + i + 1), ph, c, rb, in);
         }
         uint32_t blk[LB + 1][4];
 #pragma unroll
@@ -227,12 +197,8 @@ __device__ __forceinline__ void metrics_unit(const MetArgs &a, int k, int tile, 
         for (int i = 0; i <= kBandBlocks && b0 + i < bhc; ++i) step(i);
     }
 
-    uint64_t s64 = own ? sse : 0;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        s64 += __shfl_xor(s64, o, 64);
-        acc += __shfl_xor(acc, o, 64);
-    }
+    const uint64_t s64 = wave_sum<uint64_t>(own ? sse : 0);
+    acc = wave_sum(acc);
     __syncthreads();  // the previous unit's partial has been read
     if (lane == 0) { s_sse[wave] = s64; s_ssim[wave] = acc; }
     __syncthreads();
@@ -295,19 +261,16 @@ extern "C" int pp_metrics(pp_ctx *ctx, int fmt, int w, int h, const pp_frames *r
     MetFinal f{};
     bool aligned = true, ragged = false;
     for (int p = 0; p < 3; ++p) {
-        const int pw = p ? ceil_rshift(w, fi.hsub) : w, ph = p ? ceil_rshift(h, fi.vsub) : h;
+        PlaneGeom g = plane_geom(fmt, w, h, p);
+        const int pw = g.pw, ph = g.ph;
         const pp_frames *both[2] = {ref, dist};
         for (const pp_frames *fr : both) {
-            const int64_t ls = fr->linesize[p], fs = fr->frame_stride[p];
-            if (!fr->data[p] || ls < (int64_t)pw * bytes) PP_FAIL(PP_ERR_INVALID, "plane %d: null data or short linesize", p);
-            if (((uintptr_t)fr->data[p] | (uint64_t)ls | (uint64_t)fs) & (bytes - 1))
+            // the band's halo rows stay inside the buffer range too
+            if (int e = check_plane(fr, p, g, aligned, 4 * (kBandBlocks + 1), "", false, true)) return e;
+            if (((uintptr_t)fr->data[p] | (uint64_t)g.ls | (uint64_t)g.fs) & (bytes - 1))
                 PP_FAIL(PP_ERR_INVALID, "plane %d: 16-bit samples off the 2-byte grid", p);
-            // lane offsets and the band's halo rows stay inside the 31-bit buffer range
-            if ((int64_t)(ph + 4 * (kBandBlocks + 1)) * ls >= (int64_t)kOobOff)
-                PP_FAIL(PP_ERR_UNSUPPORTED, "plane %d of %lld bytes exceeds the 2 GiB buffer range", p, (long long)(ph * ls));
-            aligned &= !(((uintptr_t)fr->data[p] | (uint64_t)ls | (uint64_t)fs) & 15);
         }
-        ragged |= (pw % (kMetLaneBytes / bytes)) != 0;
+        ragged |= (g.rb & 15) != 0;
         a.ref[p] = static_cast<const uint8_t *>(ref->data[p]);
         a.dist[p] = static_cast<const uint8_t *>(dist->data[p]);
         a.rls[p] = ref->linesize[p]; a.rfs[p] = ref->frame_stride[p];
@@ -326,14 +289,8 @@ extern "C" int pp_metrics(pp_ctx *ctx, int fmt, int w, int h, const pp_frames *r
 
     hipStream_t st = static_cast<hipStream_t>(stream);
     PP_HIP(hipSetDevice(ctx->device));
-    const size_t need = sizeof(MetPartial) * (size_t)a.tiles * nframes;
-    if (need > ctx->met_cap) {  // grown on demand, kept by the context (hipFree waits for earlier users)
-        if (ctx->met_buf) PP_HIP(hipFree(ctx->met_buf));
-        ctx->met_buf = nullptr; ctx->met_cap = 0;
-        PP_HIP(hipMalloc(&ctx->met_buf, need));
-        ctx->met_cap = need;
-    }
-    MetPartial *part = static_cast<MetPartial *>(ctx->met_buf);
+    if (int e = grow(ctx->met, sizeof(MetPartial) * (size_t)a.tiles * nframes)) return e;
+    MetPartial *part = static_cast<MetPartial *>(ctx->met.buf);
 
     using KFn = void (*)(const MetArgs);
     const KFn k = bytes == 2 ? (!aligned ? metrics_kernel<uint16_t, false, true>

@@ -16,7 +16,8 @@
 // the plane and columns right of the row read 0 without traffic, and the bytes
 // of a ragged last piece that lie in the pitch padding are masked (RAGGED).
 // Pointers, linesizes or frame strides off the 16-B grid: the same kernel with
-// byte loads and explicit clamps (ALIGNED = false), equal results.
+// byte loads and explicit clamps (ALIGNED = false), equal results.  The piece
+// loader, its mask, the descriptor and the butterfly: analysis_dev.hpp.
 //
 // Histogram: per workgroup an LDS sub-histogram of one (frame, tile), bin-major
 // with R copies of every bin (hist[bin * R + lane % R], R = 8 for 1024 bins,
@@ -50,8 +51,8 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "common.hpp"
-#include "device.hpp"
+#include "analysis_dev.hpp"
+#include "analysis_host.hpp"
 
 namespace pp {
 
@@ -92,40 +93,6 @@ struct StatArgs {
     int abl;
 };
 
-// One 16-B piece at byte c of row `row`: zero where it lies outside the plane
-// or (RAGGED) in the pitch padding.
-template <bool ALIGNED, bool RAGGED>
-__device__ __forceinline__ void stat_load(uint32_t q[4], __amdgpu_buffer_rsrc_t rs, const uint8_t *base, int64_t ls,
-                                          int row, int ph, int c, int rb, int nb) {
-    const bool in = row < ph && nb > 0;
-    if constexpr (ALIGNED) {
-        const uint32_t voff = in ? (uint32_t)row * (uint32_t)ls + (uint32_t)c : (uint32_t)kOobOff;
-        const auto v = __builtin_amdgcn_raw_buffer_load_b128(rs, voff, 0, 0);
-        __builtin_memcpy(q, &v, 16);
-        if constexpr (RAGGED) {
-#pragma unroll
-            for (int d = 0; d < 4; ++d) {
-                const int n = nb - 4 * d;  // bytes of this dword inside the row
-                q[d] &= n >= 4 ? 0xffffffffu : n <= 0 ? 0u : (1u << (8 * n)) - 1u;
-            }
-        }
-    } else {
-        // every load goes to a byte of the plane (clamped); the select drops the others
-        const uint8_t *r = base + (int64_t)min(row, ph - 1) * ls;
-#pragma unroll
-        for (int d = 0; d < 4; ++d) {
-            uint32_t v = 0;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int x = c + 4 * d + e;
-                const uint32_t s = r[min(x, rb - 1)];
-                v |= ((in && x < rb) ? s : 0u) << (8 * e);
-            }
-            q[d] = v;
-        }
-    }
-}
-
 template <int ES, bool ALIGNED, bool RAGGED, bool SAD>
 __device__ __forceinline__ void stat_unit(const StatArgs &a, int chunk, int tile, uint32_t *hist, uint32_t *s_sad,
                                           uint32_t *s_over) {
@@ -133,7 +100,7 @@ __device__ __forceinline__ void stat_unit(const StatArgs &a, int chunk, int tile
     constexpr int R = ES == 2 ? 8 : 16;
     constexpr int SPP = kStLaneBytes / ES;  // samples per piece
     const int abl = PP_ABLATE(a.abl);
-    const int p = tile >= a.tile0[2] ? 2 : tile >= a.tile0[1] ? 1 : 0;
+    const int p = plane_of_tile(a.tile0, tile);
     const StatPlane &P = a.pl[p];
     const int t = tile - a.tile0[p];
     const int band = t / P.tx, tx = t - band * P.tx;
@@ -146,18 +113,20 @@ __device__ __forceinline__ void stat_unit(const StatArgs &a, int chunk, int tile
     const int nb = min(max(rb - c, 0), kStLaneBytes);        // bytes of a piece inside the row
     const int nvs = nb / ES;                                 // samples of a piece that count
     const int copy = (abl & kStAblNoCopies) ? 0 : lane & (R - 1);
-    // a load straddling num_records reads 0 as a whole: the last row counts up
-    // to its 16-B-rounded extent, which lies inside the (aligned) pitch
-    const int64_t wb = ((int64_t)rb + 15) & ~int64_t(15);
     const int f0 = chunk * kStFrames, f1 = min(a.nframes, f0 + kStFrames);
+    // one piece of a frame: zero where it lies outside the plane or (RAGGED) in the pitch padding
+    auto piece = [&](uint32_t q[4], __amdgpu_buffer_rsrc_t rs, const uint8_t *base, int64_t ls, int row, int nb) {
+        load_piece<uint8_t, ALIGNED>(q, rs, base, ls, row, ph, c, rb, row < ph && nb > 0);
+        if constexpr (RAGGED && ALIGNED) mask_piece(q, nb);
+    };
 
     uint32_t pv[kStLaneRows][4];
     if constexpr (SAD) {
         const uint8_t *pb = f0 > 0 ? P.data + (int64_t)(f0 - 1) * P.fs : P.prev;
         const int64_t pls = f0 > 0 ? P.ls : P.pls;
-        const auto prs = uniform_rsrc(pb, ALIGNED ? (int)((int64_t)(ph - 1) * pls + wb) : 0);
+        const auto prs = plane_rsrc<ALIGNED>(pb, ph, pls, rb);
 #pragma unroll
-        for (int u = 0; u < kStLaneRows; ++u) stat_load<ALIGNED, RAGGED>(pv[u], prs, pb, pls, r0 + u, ph, c, rb, nb);
+        for (int u = 0; u < kStLaneRows; ++u) piece(pv[u], prs, pb, pls, r0 + u, nb);
     }
 
     for (int f = f0; f < f1; ++f) {
@@ -167,13 +136,13 @@ __device__ __forceinline__ void stat_unit(const StatArgs &a, int chunk, int tile
         // (a few VALU compares) instead of holding every one as an SGPR mask
         int nbf = nb, nvf = nvs;
         asm volatile("" : "+v"(nbf), "+v"(nvf));
-        const auto rs = uniform_rsrc(base, ALIGNED ? (int)((int64_t)(ph - 1) * ls + wb) : 0);
+        const auto rs = plane_rsrc<ALIGNED>(base, ph, ls, rb);
         uint32_t sad = 0, over = 0;
 #pragma unroll
         for (int g = 0; g < kStLaneRows; g += kStGroup) {
             uint32_t q[kStGroup][4];
 #pragma unroll
-            for (int u = 0; u < kStGroup; ++u) stat_load<ALIGNED, RAGGED>(q[u], rs, base, ls, r0 + g + u, ph, c, rb, nbf);
+            for (int u = 0; u < kStGroup; ++u) piece(q[u], rs, base, ls, r0 + g + u, nbf);
 #pragma unroll
             for (int u = 0; u < kStGroup; ++u) {
                 if constexpr (SAD) {
@@ -227,11 +196,8 @@ __device__ __forceinline__ void stat_unit(const StatArgs &a, int chunk, int tile
                 }
             }
         }
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            sad += __shfl_xor(sad, o, 64);
-            over += __shfl_xor(over, o, 64);
-        }
+        sad = wave_sum(sad);
+        over = wave_sum(over);
         __syncthreads();  // every add of this frame has landed; the previous frame's sums have been read
         if (lane == 0) { s_sad[wave] = sad; s_over[wave] = over; }
         // a lane a bin: sum the copies, clear them, store the tile's histogram
@@ -305,11 +271,8 @@ __global__ __launch_bounds__(256) void stat_finalize(const uint32_t *phist, cons
         sd += x.sad;
         ov += x.over;
     }
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        sd += __shfl_xor(sd, o, 64);
-        ov += __shfl_xor(ov, o, 64);
-    }
+    sd = wave_sum(sd);
+    ov = wave_sum(ov);
     if ((threadIdx.x & 63) == 0) { s_sad[threadIdx.x >> 6] = sd; s_over[threadIdx.x >> 6] = ov; }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -336,25 +299,16 @@ extern "C" int pp_frame_stats(pp_ctx *ctx, int fmt, int w, int h, const pp_frame
     bool aligned = true, ragged = false;
     int tiles = 0;
     for (int p = 0; p < 3; ++p) {
-        const int pw = p ? ceil_rshift(w, fi.hsub) : w, ph = p ? ceil_rshift(h, fi.vsub) : h;
-        const int64_t rb = (int64_t)pw * es, ls = src->linesize[p], fs = src->frame_stride[p];
-        if (!src->data[p]) PP_FAIL(PP_ERR_INVALID, "plane %d: null data", p);
-        if (ls < rb) PP_FAIL(PP_ERR_INVALID, "plane %d: linesize %lld below the row's %lld bytes", p, (long long)ls, (long long)rb);
-        int64_t pls = ls;
-        if (prev) {
-            pls = prev->linesize[p];
-            if (!prev->data[p]) PP_FAIL(PP_ERR_INVALID, "prev plane %d: null data", p);
-            if (pls < rb)
-                PP_FAIL(PP_ERR_INVALID, "prev plane %d: linesize %lld below the row's %lld bytes", p, (long long)pls, (long long)rb);
-        }
+        PlaneGeom g = plane_geom(fmt, w, h, p), gp = g;
+        const int64_t rb = g.rb;
+        const int ph = g.ph;
         // a bin is 32 bits
-        if ((int64_t)pw * ph >= (int64_t)1 << 31)
-            PP_FAIL(PP_ERR_UNSUPPORTED, "plane %d of %lld samples (limit 2^31)", p, (long long)pw * ph);
-        // lane offsets stay inside the 31-bit buffer range
-        if ((int64_t)ph * std::max(ls, pls) >= (int64_t)kOobOff)
-            PP_FAIL(PP_ERR_UNSUPPORTED, "plane %d of %lld bytes exceeds the 2 GiB buffer range", p, (long long)(ph * std::max(ls, pls)));
-        aligned &= !(((uintptr_t)src->data[p] | (uint64_t)ls | (uint64_t)fs) & 15);
-        if (prev) aligned &= !(((uintptr_t)prev->data[p] | (uint64_t)pls) & 15);
+        if ((int64_t)g.pw * ph >= (int64_t)1 << 31)
+            PP_FAIL(PP_ERR_UNSUPPORTED, "plane %d of %lld samples (limit 2^31)", p, (long long)g.pw * ph);
+        if (int e = check_plane(src, p, g, aligned)) return e;
+        if (prev)
+            if (int e = check_plane(prev, p, gp, aligned, 0, "prev ", true)) return e;
+        const int64_t ls = g.ls, fs = g.fs, pls = prev ? gp.ls : ls;
         ragged |= (rb & 15) != 0;
         StatPlane &P = a.pl[p];
         P.data = static_cast<const uint8_t *>(src->data[p]);
@@ -375,14 +329,8 @@ extern "C" int pp_frame_stats(pp_ctx *ctx, int fmt, int w, int h, const pp_frame
     a.chunks = (nframes + kStFrames - 1) / kStFrames;
     a.total = (int64_t)a.chunks * tiles;
     const size_t units = (size_t)nframes * tiles;
-    const size_t need = units * ((size_t)bins * 4 + sizeof(StatAux));
-    if (need > ctx->stat_cap) {  // grown on demand, kept by the context (hipFree waits for earlier users)
-        if (ctx->stat_buf) PP_HIP(hipFree(ctx->stat_buf));
-        ctx->stat_buf = nullptr; ctx->stat_cap = 0;
-        PP_HIP(hipMalloc(&ctx->stat_buf, need));
-        ctx->stat_cap = need;
-    }
-    a.phist = static_cast<uint32_t *>(ctx->stat_buf);
+    if (int e = grow(ctx->stat, units * ((size_t)bins * 4 + sizeof(StatAux)))) return e;
+    a.phist = static_cast<uint32_t *>(ctx->stat.buf);
     a.paux = reinterpret_cast<StatAux *>(a.phist + units * bins);
     static const int abl = [] {
         const char *e = PP_KNOB("PIXPATH_STATS_ABL");

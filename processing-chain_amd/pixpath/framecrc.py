@@ -31,51 +31,39 @@ def hashed_format(rd, packets=False):
     return rd.fmt
 
 
-def _read_hashed(rd, n, device, packets):
+def _read_hashed(rd, n, device, window=None, packets=False):
     """Up to n frames of a reader as the device FrameBatch to hash, or None."""
-    import numpy as np
-    import torch
-
-    from . import metrics
+    from . import clips
     if rd.fmt.packed and (packets or rd.fmt.id == formats.UYVY422):
-        host = np.empty((n, rd.frame_bytes), np.uint8)
-        k = rd.read_into(host, n)
-        if k == 0:
-            return None
-        return rd.device_batch(torch.from_numpy(host[:k]).to(device))
-    return metrics._read_device(rd, n, device)
+        return clips.read_packets(rd, n, device)
+    return clips.read_device(rd, n, device)
 
 
 def checksums_of_file(path, batch=32, seed=0, packets=False):
     """PP-HASH-1 of every frame of ``path``, read with the chain's own readers
-    (metrics._open: FFV1 AVIs decoded on the GPU, v210 / UYVY AVIs by
+    (clips.open_clip: FFV1 AVIs decoded on the GPU, v210 / UYVY AVIs by
     io.PackedAviReader, anything else through io.open_reader), ``batch``
     frames at a time, hashed on the device from ``seed``.  Returns a dict:
     ``fmt`` (the name of the format hashed, see hashed_format), ``w``, ``h``,
     ``rate`` (a Fraction) and ``frames``: a list of (size_bytes, checksum),
     one per frame."""
+    import functools
+
     import torch
 
-    from . import metrics, ops
-    batch = max(1, int(batch))
-    rd = metrics._open(path, batch)
-    try:
-        dev = torch.device("cuda", torch.cuda.current_device())
+    from . import clips, ops
+    read = functools.partial(_read_hashed, packets=packets)
+    with clips.clip_batches(path, max(1, int(batch)), read=read) as (rd, _, batches):
         f = hashed_format(rd, packets)
         size = formats.frame_bytes(f, rd.w, rd.h)
         outs = []
-        while True:
-            b = _read_hashed(rd, batch, dev, packets)
-            if b is None:
-                break
+        for b in batches:
             outs.append(ops.frame_adler32(b, seed))
             # the reader may reuse its buffers on the next call
-            torch.cuda.current_stream(dev).synchronize()
+            torch.cuda.current_stream().synchronize()
         crcs = [c for o in outs for c in o.cpu().tolist()]
         return {"fmt": f.name, "w": int(rd.w), "h": int(rd.h), "rate": Fraction(rd.rate),
                 "frames": [(size, int(c)) for c in crcs]}
-    finally:
-        rd.close()
 
 
 def format_lines(frames, w, h, rate):

@@ -8,12 +8,12 @@ run on the MI355X (pp_metrics) over the decoded frames both files' readers
 already put into HBM; everything derived from them (MSE, PSNR, the frame and
 clip values) is host arithmetic in this module.
 """
-import math
 import os
 
 import numpy as np
 
 from . import formats
+from .clips import clip_batches, crop_window, json_value, planar_format  # noqa: F401
 
 PLANES = ("y", "u", "v")
 # kernel geometry (csrc/metrics.hip), for tests that place sizes on its seams
@@ -71,64 +71,6 @@ def summarize(sse, ssim, fmt, w, h):
     return res
 
 
-def _open(path, batch):
-    """The reader of a file: an AVI by its video fourcc (v210 / UYVY: the
-    packed reader, unpacked on the GPU by _read_device; anything else, FFV1
-    first of all, the FFV1 reader), other files through io.open_reader."""
-    from . import avi, ffv1, io as pio
-    if path.lower().endswith(".avi"):
-        if pio.packed_fourcc(avi.scan(path, headers_only=True)[0].get("fourcc")):
-            return pio.PackedAviReader(path)
-        return ffv1.open_avpvs_reader(path, batch=batch)
-    return pio.open_reader(path)
-
-
-def planar_format(rd):
-    """The planar format _read_device delivers a reader's frames in."""
-    if rd.fmt.packed:
-        return formats.fmt("yuv422p10le" if rd.fmt.id == formats.V210 else "yuv422p")
-    return rd.fmt
-
-
-def crop_window(W, H, w, h, crop_from="yuv422p"):
-    """(x, y, w, h) of a w x h picture on the W x H canvas where the CPVS pad
-    put it: pad_offset's rule (csrc/pack_plan.hpp, pp_pad_execute with
-    x = y = -1) -- the centring expression (outer - inner) / 2 rounded down to
-    the chroma grid of the padded format ``crop_from`` (the AVPVS's: x to even
-    for 4:2:0 and 4:2:2, y to even for 4:2:0 only)."""
-    f = formats.fmt(crop_from)
-    w, h = int(w), int(h)
-    if w < 1 or h < 1 or w > W or h > H:
-        raise ValueError("crop %dx%d does not fit the %dx%d canvas" % (w, h, W, H))
-    return (((W - w) // 2) >> f.hsub) << f.hsub, (((H - h) // 2) >> f.vsub) << f.vsub, w, h
-
-
-def _read_device(rd, n, device, window=None):
-    """Up to n frames of a reader as a planar device FrameBatch the caller
-    owns, or None.  A packed reader's packets go to the GPU as they are and are
-    unpacked there (ops.unpack), to ``window`` (x, y, w, h) if given."""
-    import torch
-
-    from .frames import FrameBatch
-    if rd.fmt.packed:
-        from . import ops
-        host = np.empty((n, rd.frame_bytes), np.uint8)
-        k = rd.read_into(host, n)
-        if k == 0:
-            return None
-        return ops.unpack(rd.device_batch(torch.from_numpy(host[:k]).to(device)), crop=window)
-    if hasattr(rd, "read_device"):
-        b = rd.read_device(n)  # a view of the reader's own buffer
-        if b is None:
-            return None
-        return FrameBatch.interleaved(rd.fmt, rd.w, rd.h, b.n, device=b.device, storage=b.storage.clone())
-    host = np.empty((n, rd.frame_bytes), np.uint8)
-    k = rd.read_into(host, n)
-    if k == 0:
-        return None
-    return FrameBatch.interleaved(rd.fmt, rd.w, rd.h, k, device=device, storage=torch.from_numpy(host[:k]).to(device))
-
-
 def _map_entries(k0, n, in_rate, out_rate, n_in=None):
     """vf_fps entries [k0, k0 + n) of the dist <- ref frame map.  Before the
     reference's length is known the map of a long enough clip is used: the two
@@ -163,14 +105,9 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, 
     from . import ops
     from .frames import FrameBatch
     batch = int(batch)
-    ref, dist = _open(ref_path, batch), _open(dist_path, batch)
-    try:
-        dev = torch.device("cuda", torch.cuda.current_device())
-        window = None
-        if crop is not None:
-            if not dist.fmt.packed:
-                raise ValueError("crop applies to a packed (v210 / UYVY) distorted clip")
-            window = crop_window(dist.w, dist.h, crop[0], crop[1], crop_from)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    with clip_batches(ref_path, batch) as (ref, _, refs), \
+            clip_batches(dist_path, batch, crop, crop_from, "distorted clip") as (dist, window, dists):
         rfmt, dfmt = planar_format(ref), planar_format(dist)
         dw, dh = (dist.w, dist.h) if window is None else window[2:]
         same = (rfmt.id, ref.w, ref.h) == (dfmt.id, dw, dh)
@@ -178,13 +115,10 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, 
         in_rate, out_rate = ref.rate, dist.rate
         win, win0, n_ref, ref_end = None, 0, 0, False  # resident reference frames [win0, n_ref), dist geometry
         outs, k0 = [], 0
-        while True:
-            d = _read_device(dist, batch, dev, window)
-            if d is None:
-                break
+        for d in dists:
             m = _map_entries(k0, d.n, in_rate, out_rate)
             while not ref_end and n_ref <= int(m[-1]):
-                r = _read_device(ref, batch, dev)
+                r = next(refs, None)
                 if r is None:
                     ref_end = True
                     break
@@ -210,9 +144,6 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, 
             outs.append(ops.metrics(win, d, ref_index=m - win0))
             k0 += d.n
         torch.cuda.current_stream(dev).synchronize()
-    finally:
-        ref.close()
-        dist.close()
     if outs:
         sse = torch.cat([o[0] for o in outs]).cpu().numpy()
         ssim = torch.cat([o[1] for o in outs]).cpu().numpy()
@@ -221,21 +152,16 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, 
     return summarize(sse, ssim, dfmt, dw, dh)
 
 
-def _json_value(v):
-    v = float(v)
-    return v if math.isfinite(v) else None
-
-
 def report(res, ref_path, dist_path, per_frame=False):
     """The JSON object `cli metrics` prints: clip values, and with per_frame
     the per-frame lists; NaN and infinite values become null."""
     out = {"ref": os.path.basename(ref_path), "file": os.path.basename(dist_path), "frames": int(res["frames"]),
            "spec": "PP-METRIC-1"}
     for k, v in res["mean"].items():
-        out[k] = _json_value(v)
+        out[k] = json_value(v)
     if per_frame:
         for kind in ("mse", "psnr", "ssim"):
             for name in PLANES + ("all",):
                 key = "%s_%s" % (kind, name)
-                out[key + "_frames"] = [_json_value(v) for v in res[key]]
+                out[key + "_frames"] = [json_value(v) for v in res[key]]
     return out

@@ -20,6 +20,7 @@ import os
 import numpy as np
 
 from . import formats
+from .clips import json_value
 
 PLANES = ("y", "u", "v")
 SAD_ABSENT = (1 << 64) - 1  # pp_frame_stats' sad[0] without a previous frame
@@ -143,40 +144,27 @@ def arrays_of_file(path, batch=32, crop=None, crop_from="yuv422p"):
     """pp_frame_stats over every frame of ``path``: (hist, sad, over, fmt, w, h)
     with numpy arrays [N, 3, bins] int32, [N, 3] uint64, [N, 3] int32 and the
     planar format and size they describe.  The file is opened as `cli metrics`
-    opens its inputs (metrics._open / _read_device: an FFV1 AVI through the GPU
-    decoder, a v210 / UYVY AVI unpacked on the GPU to yuv422p10le / yuv422p,
-    anything else through io.open_reader) and streamed ``batch`` frames at a
-    time; the last frame of a batch is the next call's ``prev``, so only frame
-    0 of the file has no difference.  ``crop`` = (w, h): the file is a packed
-    CPVS canvas and only the w x h AVPVS picture inside it counts, at the
-    offsets the CPVS pad put it (metrics.crop_window; ``crop_from``: the
-    AVPVS's pixel format) -- without it a letterboxed CPVS's bars dominate
-    every statistic."""
+    opens its inputs (clips.open_clip / read_device: an FFV1 AVI through the
+    GPU decoder, a v210 / UYVY AVI unpacked on the GPU to yuv422p10le /
+    yuv422p, anything else through io.open_reader) and streamed ``batch``
+    frames at a time; the last frame of a batch is the next call's ``prev``,
+    so only frame 0 of the file has no difference.  ``crop`` = (w, h): the
+    file is a packed CPVS canvas and only the w x h AVPVS picture inside it
+    counts, at the offsets the CPVS pad put it (clips.crop_window;
+    ``crop_from``: the AVPVS's pixel format) -- without it a letterboxed
+    CPVS's bars dominate every statistic."""
     import torch
 
-    from . import metrics, ops
+    from . import clips, ops
     from .frames import FrameBatch
-    batch = max(1, int(batch))
-    rd = metrics._open(path, batch)
-    try:
-        dev = torch.device("cuda", torch.cuda.current_device())
-        window = None
-        if crop is not None:
-            if not rd.fmt.packed:
-                raise ValueError("crop applies to a packed (v210 / UYVY) clip")
-            window = metrics.crop_window(rd.w, rd.h, crop[0], crop[1], crop_from)
-        f = metrics.planar_format(rd)
+    with clips.clip_batches(path, max(1, int(batch)), crop, crop_from) as (rd, window, batches):
+        f = clips.planar_format(rd)
         w, h = (rd.w, rd.h) if window is None else window[2:]
         outs, prev = [], None
-        while True:
-            b = metrics._read_device(rd, batch, dev, window)
-            if b is None:
-                break
+        for b in batches:
             outs.append(ops.frame_stats(b, prev=prev))
             prev = FrameBatch(f, w, h, 1, planes=[t[b.n - 1:b.n] for t in b.planes])
-        torch.cuda.current_stream(dev).synchronize()
-    finally:
-        rd.close()
+        torch.cuda.current_stream().synchronize()
     bins = 1 << f.depth
     if outs:
         hist = torch.cat([o[0] for o in outs]).cpu().numpy()
@@ -197,15 +185,6 @@ def stats_of_file(path, batch=32, crop=None, crop_from="yuv422p", pix_th=BLACK_P
     return res
 
 
-def _json_value(v):
-    if isinstance(v, (bool, np.bool_)):
-        return bool(v)
-    if isinstance(v, (int, np.integer)):
-        return int(v)
-    v = float(v)
-    return v if math.isfinite(v) else None
-
-
 def report(res, path, per_frame=False):
     """The JSON object `cli stats` prints: the clip values, and with per_frame
     the per-frame lists (``<name>_<plane>_frames``, ``black``, ``repeat``); NaN
@@ -215,12 +194,12 @@ def report(res, path, per_frame=False):
         if k in res:
             out[k] = res[k]
     for k, v in res["clip"].items():
-        out[k] = v if isinstance(v, list) else _json_value(v)
+        out[k] = v if isinstance(v, list) else json_value(v)
     if per_frame:
         for kind in PER_PLANE:
             for name in PLANES:
                 key = "%s_%s" % (kind, name)
-                out[key + "_frames"] = [_json_value(v) for v in res[key]]
+                out[key + "_frames"] = [json_value(v) for v in res[key]]
         out["black"] = [bool(v) for v in res["black"]]
         out["repeat"] = [bool(v) for v in res["repeat"]]
     return out

@@ -11,7 +11,7 @@ import pytest
 
 import pyoracle as po
 import unpack_ref
-from pixpath import _native, avi, formats, io as pio, metrics
+from pixpath import _native, avi, clips, formats, io as pio, metrics
 
 
 def _planes(rng, w, h, n=None, depth=10):
@@ -241,10 +241,10 @@ def test_metrics_open_routes_by_fourcc(tmp_path, monkeypatch):
     monkeypatch.setattr(ffv1, "open_avpvs_reader", lambda path, batch=None: ("ffv1", path, batch))
     monkeypatch.setattr(pio, "PackedAviReader", lambda path: ("packed", path))
     monkeypatch.setattr(pio, "open_reader", lambda path, *a, **k: ("plain", path))
-    assert metrics._open(f_ffv1, 7) == ("ffv1", f_ffv1, 7)
-    assert metrics._open(f_v210, 7) == ("packed", f_v210)
-    assert metrics._open(f_uyvy, 7) == ("packed", f_uyvy)
-    assert metrics._open("/x/src.y4m", 7) == ("plain", "/x/src.y4m")
+    assert clips.open_clip(f_ffv1, 7) == ("ffv1", f_ffv1, 7)
+    assert clips.open_clip(f_v210, 7) == ("packed", f_v210)
+    assert clips.open_clip(f_uyvy, 7) == ("packed", f_uyvy)
+    assert clips.open_clip("/x/src.y4m", 7) == ("plain", "/x/src.y4m")
 
 
 def test_crop_window_is_the_pads_offset():
