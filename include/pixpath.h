@@ -419,6 +419,35 @@ int pp_frame_stats(pp_ctx *ctx, int fmt, int w, int h, const pp_frames *src,
                    int nframes, const pp_frames *prev,
                    uint32_t *hist, uint64_t *sad, uint32_t *over, void *stream);
 
+/* ---- luma SSE of every distorted frame against a band of reference frames
+ * (spec PP-ALIGN-1) -------------------------------------------
+ * The sums a temporal alignment searches: dist holds ndist luma planes of
+ * w x h samples, ref holds nref of them, each with a pitch and frame stride of
+ * its own.  bitdepth 8: bytes; 10: uint16 LE taken as stored, nothing masked
+ * (as pp_metrics and pp_frame_stats).  first: HOST array of ndist entries.
+ *   sse [ndist][ncand] uint64, DEVICE, every element written:
+ *        sse[k][c] = sum over the w x h samples of
+ *        (dist[k] - ref[first[k] + c])^2, exact; UINT64_MAX (absent, as
+ *        pp_frame_stats' sad) where first[k] + c lies outside [0, nref).
+ *        A negative first[k] only makes the leading candidates absent.
+ * Pitch padding never counts.  The results are exact integers and identical
+ * from run to run for every stored 16-bit value.  NULL ctx, dist, ref, first
+ * or sse, w or h < 1, ndist or nref < 0, ncand < 1, a linesize below the row's
+ * bytes, 16-bit samples off the 2-byte grid and a bitdepth other than 8 or 10
+ * are PP_ERR_INVALID; a plane past the 2 GiB buffer range is
+ * PP_ERR_UNSUPPORTED.  Arguments are checked before any HIP call; ndist == 0
+ * is PP_OK and writes nothing.  Sources on the 16-byte grid (both pointers,
+ * linesizes and frame strides) are read with 16-byte loads, dist once and ref
+ * once per candidate; if either is off the grid both are read element by
+ * element, with identical results.  The workspace (one partial per
+ * frame, candidate and 64-row x 1024-byte tile) belongs to the context.  No
+ * reference implementation exists: parity is unpinned.  Added without raising
+ * PP_ABI_VERSION (still 7). */
+int pp_frame_sse_band(pp_ctx *ctx, int bitdepth, int w, int h,
+                      const void *dist, int64_t dist_linesize, int64_t dist_frame_stride, int ndist,
+                      const void *ref, int64_t ref_linesize, int64_t ref_frame_stride, int nref,
+                      const int32_t *first, int ncand, uint64_t *sse, void *stream);
+
 /* ---- host helpers --------------------------------------------------------
  * vf_fps output->input frame map (lib/ffmpeg.py:832-834, :959-961, :1038,
  * :1179): map[k] = input frame shown at output frame k.  Returns the number of

@@ -116,9 +116,9 @@ struct Ctx {
     int spin_fmt = -1, spin_n = 0, spin_w = 0, spin_h = 0;
     void *spin_buf = nullptr; // [n][Y(w*h) A(w*h) U V Ac (cw*ch each)] uint16
     // partials of pp_metrics (PP-METRIC-1) and pp_frame_adler32 (PP-HASH-1), tile
-    // histograms of pp_frame_stats (PP-STATS-1).  One each: the three may be
-    // enqueued on different streams at once.
-    Scratch met, crc, stat;
+    // histograms of pp_frame_stats (PP-STATS-1), partials of pp_frame_sse_band
+    // (PP-ALIGN-1).  One each: the four may be enqueued on different streams at once.
+    Scratch met, crc, stat, aln;
 };
 
 } // namespace pp

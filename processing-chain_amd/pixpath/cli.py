@@ -19,6 +19,8 @@ the ffmpeg strings they replace).
           --against FILE compares with a listing; `avpvs --framecrc FILE` lists what the writer was given
   stats  what is inside one clip (spec PP-STATS-1): per-plane range, mean, percentiles, used bits,
           out-of-range and out-of-container samples, black and repeated frames, from one GPU pass
+  align  which SRC frame every frame of a PVS shows (spec PP-ALIGN-1): stalls and freezes as holds, jumps as
+          skips, black lead-ins as unmatched frames; `metrics --align` scores with that map
 
 Inputs/outputs ending in .y4m or .raw/.yuv are read/written directly;
 anything else goes through ffmpeg pipes.  The device is PIXPATH_DEVICE, else
@@ -655,8 +657,48 @@ def cmd_metrics(args):
             kw["crop_from"] = args.avpvs_pix_fmt
     elif args.avpvs_pix_fmt:
         raise SystemExit("--avpvs-pix-fmt needs --crop")
+    extra = {}
+    if args.align:  # pair the frames by their pictures (spec PP-ALIGN-1), not by the vf_fps map
+        from . import align
+        al = align.align_files(args.ref, args.input, batch=args.batch, flags=args.flags, **_align_settings(args), **kw)
+        kw["ref_index"] = al["map"]
+        extra = {"aligned": True, "unmatched": int((al["map"] < 0).sum())}
+    elif args.lookahead is not None or args.min_psnr is not None:
+        raise SystemExit("--lookahead and --min-psnr need --align")
     res = metrics.metrics_of_files(args.ref, args.input, batch=args.batch, flags=args.flags, **kw)
-    print(json.dumps(metrics.report(res, args.ref, args.input, per_frame=args.per_frame)))
+    out = metrics.report(res, args.ref, args.input, per_frame=args.per_frame)
+    out.update(extra)
+    print(json.dumps(out))
+    return 0
+
+
+def _crop_settings(args):
+    kw = {}
+    if args.crop:  # a CPVS canvas: the AVPVS picture inside it
+        cw, ch = args.crop.lower().split("x")
+        kw["crop"] = (int(cw), int(ch))
+        if args.avpvs_pix_fmt:
+            kw["crop_from"] = args.avpvs_pix_fmt
+    elif args.avpvs_pix_fmt:
+        raise SystemExit("--avpvs-pix-fmt needs --crop")
+    return kw
+
+
+def _align_settings(args):
+    kw = {}
+    if args.lookahead is not None:
+        kw["lookahead"] = args.lookahead
+    if args.min_psnr is not None:
+        kw["min_psnr"] = args.min_psnr
+    return kw
+
+
+def cmd_align(args):
+    """Which SRC frame every frame of a PVS shows (spec PP-ALIGN-1): one JSON line."""
+    from . import align
+    res = align.align_files(args.ref, args.input, batch=args.batch, flags=args.flags, **_align_settings(args),
+                            **_crop_settings(args))
+    print(json.dumps(align.report(res, args.ref, args.input, per_frame=args.per_frame)))
     return 0
 
 
@@ -801,7 +843,25 @@ def main(argv=None):
                    help="the input is a v210 / UYVY CPVS: compare the WxH AVPVS picture inside its canvas")
     p.add_argument("--avpvs-pix-fmt", default=None, metavar="NAME",
                    help="pixel format of the AVPVS the CPVS was padded from (yuv420p...: rows offset rounded to even)")
+    p.add_argument("--align", action="store_true",
+                   help="pair the frames by temporal alignment (spec PP-ALIGN-1) instead of the vf_fps map")
+    p.add_argument("--lookahead", type=int, default=None, help="with --align: reference frames searched ahead (64)")
+    p.add_argument("--min-psnr", type=float, default=None, help="with --align: luma PSNR a match needs, in dB (14)")
     p.set_defaults(fn=cmd_metrics)
+
+    p = sub.add_parser("align")
+    p.add_argument("--ref", required=True, help="the source clip (SRC)")
+    p.add_argument("--input", required=True, help="the distorted clip (PVS)")
+    p.add_argument("--batch", type=int, default=32)
+    p.add_argument("--flags", default="bicubic", help="scaler bringing the SRC to the input's size and format")
+    p.add_argument("--per-frame", action="store_true", help="add the map and the matches' luma PSNR")
+    p.add_argument("--lookahead", type=int, default=None, help="reference frames searched ahead of the cursor (64)")
+    p.add_argument("--min-psnr", type=float, default=None, help="luma PSNR a match needs, in dB (14)")
+    p.add_argument("--crop", default=None, metavar="WxH",
+                   help="the input is a v210 / UYVY CPVS: align the WxH AVPVS picture inside its canvas")
+    p.add_argument("--avpvs-pix-fmt", default=None, metavar="NAME",
+                   help="pixel format of the AVPVS the CPVS was padded from (yuv420p...: rows offset rounded to even)")
+    p.set_defaults(fn=cmd_align)
 
     p = sub.add_parser("framecrc")
     p.add_argument("input", metavar="INPUT")

@@ -32,14 +32,16 @@ def _psnr(mse, peak):
     return out
 
 
-def summarize(sse, ssim, fmt, w, h):
+def summarize(sse, ssim, fmt, w, h, matched=None):
     """Host side of PP-METRIC-1: per-frame arrays ``mse_y/u/v/all``,
     ``psnr_y/u/v/all``, ``ssim_y/u/v/all`` (float64 [N]) from pp_metrics' sums
     (sse [N, 3] integers, ssim [N, 3]), plus ``mean``: the clip values (mean
     MSE, PSNR of the mean MSE, mean SSIM over the frames that have one).
     Identical planes (MSE 0) have no PSNR: NaN.  ``all``: MSE over the samples
     of all planes; SSIM weighted by plane size over the planes whose SSIM is
-    defined."""
+    defined.  ``matched`` (bool [N], an explicit frame map's): the other frames
+    have no reference frame; their rows are NaN and the clip values leave them
+    out."""
     f = formats.fmt(fmt)
     sse = np.asarray(sse).reshape(-1, 3)
     ssim = np.asarray(ssim, dtype=np.float64).reshape(-1, 3)
@@ -58,9 +60,15 @@ def summarize(sse, ssim, fmt, w, h):
     res["ssim_all"] = np.where(wsum > 0, num / np.where(wsum > 0, wsum, 1.0), np.nan)
     for name in PLANES + ("all",):
         res["psnr_" + name] = _psnr(res["mse_" + name], peak)
+    if matched is not None:
+        matched = np.asarray(matched, dtype=bool)
+        for key in res:
+            res[key][~matched] = np.nan
     mean = {}
     for name in PLANES + ("all",):
         m = res["mse_" + name]
+        if matched is not None:
+            m = m[matched]
         mean["mse_" + name] = float(m.mean()) if m.size else float("nan")
         mean["psnr_" + name] = float(_psnr(mean["mse_" + name], peak))
         s = res["ssim_" + name]
@@ -82,7 +90,7 @@ def _map_entries(k0, n, in_rate, out_rate, n_in=None):
     return ops.fps_map(n_in, in_rate, out_rate)[k0:k0 + n]
 
 
-def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, crop_from="yuv422p"):
+def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, crop_from="yuv422p", ref_index=None):
     """PP-METRIC-1 of the file ``dist_path`` (the PVS) against ``ref_path``
     (the SRC); returns ``summarize``'s dict.  Both are read with the chain's
     own readers (FFV1 AVIs through ffv1.open_avpvs_reader, anything else
@@ -99,7 +107,14 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, 
     the w x h AVPVS picture inside it is compared, at the offsets the CPVS pad
     put it (crop_window; ``crop_from``: the AVPVS's pixel format, which decides
     the rounding of the offsets -- pass "yuv420p" / "yuv420p10le" for a 4:2:0
-    AVPVS).  Without ``crop`` the whole canvas is compared."""
+    AVPVS).  Without ``crop`` the whole canvas is compared.
+
+    ``ref_index`` (one int per distorted frame, pixpath.align's ``map``)
+    replaces the vf_fps map: distorted frame k is compared with reference
+    frame ref_index[k], the matched entries never going back; a frame with
+    ref_index[k] < 0 has no reference frame: its rows are NaN and the clip
+    values leave it out.  The comparison ends with the shorter of the
+    distorted clip and the map."""
     import torch
 
     from . import ops
@@ -115,8 +130,21 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, 
         in_rate, out_rate = ref.rate, dist.rate
         win, win0, n_ref, ref_end = None, 0, 0, False  # resident reference frames [win0, n_ref), dist geometry
         outs, k0 = [], 0
+        explicit = None if ref_index is None else np.asarray(ref_index, dtype=np.int64).reshape(-1)
+        last = 0  # explicit map: the reference frame an unmatched distorted frame is read against (and not reported)
         for d in dists:
-            m = _map_entries(k0, d.n, in_rate, out_rate)
+            if explicit is None:
+                m = _map_entries(k0, d.n, in_rate, out_rate)
+            else:
+                m = explicit[k0:k0 + d.n].copy()
+                if len(m) == 0:
+                    break
+                for i in range(len(m)):
+                    if m[i] < 0:
+                        m[i] = last
+                    elif m[i] < last:
+                        raise ValueError("ref_index goes back from %d to %d at frame %d" % (last, m[i], k0 + i))
+                    last = int(m[i])
             while not ref_end and n_ref <= int(m[-1]):
                 r = next(refs, None)
                 if r is None:
@@ -135,7 +163,10 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, 
                         nw.view(p)[k1:].copy_(r.view(p))
                     win, win0 = nw, win0 + keep
                 n_ref += r.n
-            if ref_end:  # the reference's length is known now: the map's true end and clamp
+            if ref_end and explicit is not None:
+                if int(m[-1]) >= n_ref:
+                    raise ValueError("ref_index names frame %d of a reference of %d frames" % (int(m[-1]), n_ref))
+            elif ref_end:  # the reference's length is known now: the map's true end and clamp
                 m = _map_entries(k0, d.n, in_rate, out_rate, n_in=n_ref)
             if len(m) == 0 or win is None:
                 break
@@ -149,7 +180,9 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, 
         ssim = torch.cat([o[1] for o in outs]).cpu().numpy()
     else:
         sse, ssim = np.zeros((0, 3), np.int64), np.zeros((0, 3))
-    return summarize(sse, ssim, dfmt, dw, dh)
+    if explicit is None:
+        return summarize(sse, ssim, dfmt, dw, dh)
+    return summarize(sse, ssim, dfmt, dw, dh, matched=explicit[:sse.shape[0]] >= 0)
 
 
 def report(res, ref_path, dist_path, per_frame=False):

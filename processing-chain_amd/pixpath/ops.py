@@ -375,6 +375,56 @@ def frame_stats(batch, prev=None, want_sad=True, stream=None):
     return hist, sad, over
 
 
+def _luma(x):
+    """([N, H, W] luma tensor, bit depth) of a FrameBatch or of such a tensor
+    (uint8: 8 bits, uint16: the 10-bit container)."""
+    if hasattr(x, "planes"):
+        if x.fmt.packed:
+            raise ValueError("sse_band takes planar frames: unpack %s first (ops.unpack)" % x.fmt.name)
+        return x.view(0), x.fmt.depth
+    if x.dim() != 3 or (x.shape[2] > 1 and x.stride(2) != 1):
+        raise ValueError("luma must be [N, H, W] with contiguous rows")
+    if x.dtype not in (torch.uint8, torch.uint16):
+        raise ValueError("luma must be uint8 or uint16")
+    return x, 8 if x.dtype == torch.uint8 else 10
+
+
+def sse_band(ref_batch, dist_batch, first, ncand, stream=None):
+    """Luma SSE of every frame of ``dist_batch`` against a band of ``ncand``
+    frames of ``ref_batch`` (spec PP-ALIGN-1, pp_frame_sse_band): two
+    FrameBatches of one size and bit depth, or their [N, H, W] luma tensors
+    (any pitches).  ``first``: one int per distorted frame, the reference index
+    of its candidate 0 (negative allowed).  Returns a device tensor int64
+    [ndist, ncand] on the current stream: out[k, c] = sum (dist[k] -
+    ref[first[k] + c])^2, exact, or -1 (the kernel's UINT64_MAX read as int64:
+    absent) where first[k] + c is no frame of ``ref_batch``."""
+    r, rd = _luma(ref_batch)
+    d, dd = _luma(dist_batch)
+    if rd != dd or tuple(r.shape[1:]) != tuple(d.shape[1:]):
+        raise ValueError("ref and dist differ in bit depth or size")
+    if r.device != d.device:
+        raise ValueError("ref and dist are on different devices")
+    n, h, w = d.shape
+    fi = np.ascontiguousarray(first, dtype=np.int32)
+    if fi.shape != (n,):
+        raise ValueError("first needs one entry per dist frame")
+    ncand = int(ncand)
+    if ncand < 1:
+        raise ValueError("ncand must be at least 1")
+    out = torch.empty((n, ncand), dtype=torch.int64, device=d.device)
+    if n == 0:  # an empty batch has no data pointer to pass
+        return out
+    es = d.element_size()
+    ctx = context(d.device.index)
+    # an empty reference has no data pointer: dist's stands in (no candidate exists, nothing is read)
+    rp = r.data_ptr() if r.shape[0] else d.data_ptr()
+    check(lib().pp_frame_sse_band(ctx.handle, dd, w, h, ctypes.c_void_p(d.data_ptr()), d.stride(1) * es,
+                                  d.stride(0) * es, n, ctypes.c_void_p(rp), r.stride(1) * es, r.stride(0) * es,
+                                  r.shape[0], fi.ctypes.data, ncand, ctypes.c_void_p(out.data_ptr()),
+                                  _stream(d, stream)))
+    return out
+
+
 def spinner_upload(rgba_frames, f, device=None):
     """Upload an RGBA8 animation [n, h, w, 4] (host) for stall compositing."""
     a = np.ascontiguousarray(rgba_frames, dtype=np.uint8)
