@@ -448,6 +448,46 @@ int pp_frame_sse_band(pp_ctx *ctx, int bitdepth, int w, int h,
                       const void *ref, int64_t ref_linesize, int64_t ref_frame_stride, int nref,
                       const int32_t *first, int ncand, uint64_t *sse, void *stream);
 
+/* ---- multi-scale SSIM of a distorted luma batch against its reference
+ * (spec PP-MSSSIM-1) ------------------------------------------
+ * MS-SSIM after Wang, Simoncelli & Bovik 2003, the metric between pp_metrics'
+ * block SSIM and VMAF: five dyadic scales (scale s = the means of the 2^s x 2^s
+ * blocks, trailing w mod 2^s columns and h mod 2^s rows dropped), an 11 x 11
+ * Gaussian window (sigma 1.5) at every position where all 121 samples exist,
+ * K1 = .01, K2 = .03, L = 2^bitdepth - 1.  ref holds nref luma planes of
+ * w x h samples, dist holds ndist of them, each with a pitch and frame stride
+ * of its own.  bitdepth 8: bytes; 10: uint16 LE taken as stored, nothing masked
+ * (as pp_frame_sse_band).  dist frame k is compared with ref frame
+ * ref_index[k] (HOST array of ndist entries, NULL = identity, which needs
+ * ndist <= nref; an entry outside [0, nref) is PP_ERR_INVALID).
+ *   out [ndist][5][2] double, DEVICE, every element written and nothing else:
+ *        out[k][s][0] = mean of cs = (2 sigma_ab + C2) / (sigma_a^2 +
+ *        sigma_b^2 + C2) over the (w_s - 10)(h_s - 10) windows of scale s,
+ *        out[k][s][1] = mean of l * cs (the scale's SSIM; s = 0 is the
+ *        Gaussian-window SSIM of the 2004 paper); both NaN for a scale under
+ *        11 samples wide or high.  Scale 4 has a window from 176 x 176 on.
+ * The five exponents and the product (clamping negative means to 0) are host
+ * arithmetic: pixpath/msssim.py `pool`.  The number of scales is fixed by the
+ * paper's exponents, so the call has no scale-count argument.  Everything is
+ * fp64 on exact integer pyramids; identical planes give exactly 1.0, and two
+ * runs give the same bits (no atomics, partials added in a fixed order).
+ * Pitch padding never counts.  NULL ctx, ref, dist or out, w or h < 1, ndist or
+ * nref < 0, a linesize below the row's bytes, 16-bit samples off the 2-byte
+ * grid and a bitdepth other than 8 or 10 are PP_ERR_INVALID; a plane past the
+ * 2 GiB buffer range is PP_ERR_UNSUPPORTED.  Arguments are checked before any
+ * HIP call; ndist == 0 is PP_OK and writes nothing.  Every sample is loaded as
+ * one element, whatever grid the pointers, linesizes and frame strides lie on:
+ * the kernel is bound by its arithmetic, and the layout of the same samples
+ * cannot change a bit of the result.  The workspace (both integer pyramids of
+ * up to 256 frames or 1 GiB a launch, one partial per frame, scale and tile of
+ * 256 x 64 windows) belongs to the context.  Parity with libvmaf's
+ * float_ms_ssim, which downsamples with another low-pass filter, is unpinned.
+ * Added without raising PP_ABI_VERSION (still 7). */
+int pp_ms_ssim(pp_ctx *ctx, int bitdepth, int w, int h,
+               const void *ref, int64_t ref_linesize, int64_t ref_frame_stride, int nref,
+               const void *dist, int64_t dist_linesize, int64_t dist_frame_stride, int ndist,
+               const int32_t *ref_index, double *out, void *stream);
+
 /* ---- host helpers --------------------------------------------------------
  * vf_fps output->input frame map (lib/ffmpeg.py:832-834, :959-961, :1038,
  * :1179): map[k] = input frame shown at output frame k.  Returns the number of

@@ -14,7 +14,8 @@ the ffmpeg strings they replace).
   preview AVPVS decoded here (GPU FFV1) -> ffmpeg's ProRes (create_preview :1250)
   siti   P.910 SI/TI of a SRC (util/SRC_analysis.py hook)
   metrics per-frame PSNR / SSIM of a PVS against its SRC (spec PP-METRIC-1; after p03);
-          --crop WxH [--avpvs-pix-fmt NAME] scores a v210 / UYVY CPVS against its AVPVS
+          --crop WxH [--avpvs-pix-fmt NAME] scores a v210 / UYVY CPVS against its AVPVS;
+          --ms-ssim adds the luma MS-SSIM and Gaussian-window SSIM (spec PP-MSSSIM-1)
   framecrc FFmpeg's `-f framecrc` listing of a file: one GPU Adler-32 per frame (spec PP-HASH-1);
           --against FILE compares with a listing; `avpvs --framecrc FILE` lists what the writer was given
   stats  what is inside one clip (spec PP-STATS-1): per-plane range, mean, percentiles, used bits,
@@ -665,6 +666,8 @@ def cmd_metrics(args):
         extra = {"aligned": True, "unmatched": int((al["map"] < 0).sum())}
     elif args.lookahead is not None or args.min_psnr is not None:
         raise SystemExit("--lookahead and --min-psnr need --align")
+    if args.ms_ssim:  # luma MS-SSIM and Gaussian-window SSIM as well (spec PP-MSSSIM-1)
+        kw["ms_ssim"] = True
     res = metrics.metrics_of_files(args.ref, args.input, batch=args.batch, flags=args.flags, **kw)
     out = metrics.report(res, args.ref, args.input, per_frame=args.per_frame)
     out.update(extra)
@@ -847,6 +850,8 @@ def main(argv=None):
                    help="pair the frames by temporal alignment (spec PP-ALIGN-1) instead of the vf_fps map")
     p.add_argument("--lookahead", type=int, default=None, help="with --align: reference frames searched ahead (64)")
     p.add_argument("--min-psnr", type=float, default=None, help="with --align: luma PSNR a match needs, in dB (14)")
+    p.add_argument("--ms-ssim", action="store_true",
+                   help="add the luma MS-SSIM and Gaussian-window SSIM (spec PP-MSSSIM-1)")
     p.set_defaults(fn=cmd_metrics)
 
     p = sub.add_parser("align")

@@ -32,7 +32,7 @@ def _psnr(mse, peak):
     return out
 
 
-def summarize(sse, ssim, fmt, w, h, matched=None):
+def summarize(sse, ssim, fmt, w, h, matched=None, ms_terms=None):
     """Host side of PP-METRIC-1: per-frame arrays ``mse_y/u/v/all``,
     ``psnr_y/u/v/all``, ``ssim_y/u/v/all`` (float64 [N]) from pp_metrics' sums
     (sse [N, 3] integers, ssim [N, 3]), plus ``mean``: the clip values (mean
@@ -41,7 +41,10 @@ def summarize(sse, ssim, fmt, w, h, matched=None):
     of all planes; SSIM weighted by plane size over the planes whose SSIM is
     defined.  ``matched`` (bool [N], an explicit frame map's): the other frames
     have no reference frame; their rows are NaN and the clip values leave them
-    out."""
+    out.  ``ms_terms`` (pp_ms_ssim's [N, 5, 2], spec PP-MSSSIM-1; only when
+    asked for): adds ``ms_ssim_y``, ``ssim_gauss_y`` [N], ``cs_scales_y`` and
+    ``ssim_scales_y`` [N, 5] and the clip means of the first two
+    (msssim.summarize)."""
     f = formats.fmt(fmt)
     sse = np.asarray(sse).reshape(-1, 3)
     ssim = np.asarray(ssim, dtype=np.float64).reshape(-1, 3)
@@ -76,6 +79,11 @@ def summarize(sse, ssim, fmt, w, h, matched=None):
         mean["ssim_" + name] = float(s.mean()) if s.size else float("nan")
     res["mean"] = mean
     res["frames"] = int(sse.shape[0])
+    if ms_terms is not None:
+        from . import msssim
+        ms = msssim.summarize(ms_terms, matched)
+        mean.update(ms.pop("mean"))
+        res.update(ms)
     return res
 
 
@@ -90,7 +98,8 @@ def _map_entries(k0, n, in_rate, out_rate, n_in=None):
     return ops.fps_map(n_in, in_rate, out_rate)[k0:k0 + n]
 
 
-def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, crop_from="yuv422p", ref_index=None):
+def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, crop_from="yuv422p", ref_index=None,
+                     ms_ssim=False):
     """PP-METRIC-1 of the file ``dist_path`` (the PVS) against ``ref_path``
     (the SRC); returns ``summarize``'s dict.  Both are read with the chain's
     own readers (FFV1 AVIs through ffv1.open_avpvs_reader, anything else
@@ -114,7 +123,10 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, 
     frame ref_index[k], the matched entries never going back; a frame with
     ref_index[k] < 0 has no reference frame: its rows are NaN and the clip
     values leave it out.  The comparison ends with the shorter of the
-    distorted clip and the map."""
+    distorted clip and the map.
+
+    ``ms_ssim``: also the luma MS-SSIM and Gaussian-window SSIM of every frame
+    pair (spec PP-MSSSIM-1, ops.ms_ssim on the same resident frames)."""
     import torch
 
     from . import ops
@@ -129,7 +141,7 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, 
         scaler = None if same else ops.Scaler(rfmt, ref.w, ref.h, dfmt, dw, dh, flags=flags, device=dev)
         in_rate, out_rate = ref.rate, dist.rate
         win, win0, n_ref, ref_end = None, 0, 0, False  # resident reference frames [win0, n_ref), dist geometry
-        outs, k0 = [], 0
+        outs, terms, k0 = [], [], 0
         explicit = None if ref_index is None else np.asarray(ref_index, dtype=np.int64).reshape(-1)
         last = 0  # explicit map: the reference frame an unmatched distorted frame is read against (and not reported)
         for d in dists:
@@ -173,6 +185,8 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, 
             if len(m) < d.n:
                 d = FrameBatch(dfmt, dw, dh, len(m), device=d.device, planes=[t[:len(m)] for t in d.planes])
             outs.append(ops.metrics(win, d, ref_index=m - win0))
+            if ms_ssim:
+                terms.append(ops.ms_ssim(win, d, ref_index=m - win0))
             k0 += d.n
         torch.cuda.current_stream(dev).synchronize()
     if outs:
@@ -180,14 +194,20 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, 
         ssim = torch.cat([o[1] for o in outs]).cpu().numpy()
     else:
         sse, ssim = np.zeros((0, 3), np.int64), np.zeros((0, 3))
+    ms = None
+    if ms_ssim:
+        ms = torch.cat(terms).cpu().numpy() if terms else np.zeros((0, 5, 2))
     if explicit is None:
-        return summarize(sse, ssim, dfmt, dw, dh)
-    return summarize(sse, ssim, dfmt, dw, dh, matched=explicit[:sse.shape[0]] >= 0)
+        return summarize(sse, ssim, dfmt, dw, dh, ms_terms=ms)
+    return summarize(sse, ssim, dfmt, dw, dh, matched=explicit[:sse.shape[0]] >= 0, ms_terms=ms)
 
 
 def report(res, ref_path, dist_path, per_frame=False):
     """The JSON object `cli metrics` prints: clip values, and with per_frame
-    the per-frame lists; NaN and infinite values become null."""
+    the per-frame lists; NaN and infinite values become null.  A result with
+    MS-SSIM (summarize's ms_terms) adds ``ms_ssim_y``, ``ssim_gauss_y`` and,
+    per frame, those two and the per-scale means ``cs_scales_y_frames`` /
+    ``ssim_scales_y_frames`` ([N][5])."""
     out = {"ref": os.path.basename(ref_path), "file": os.path.basename(dist_path), "frames": int(res["frames"]),
            "spec": "PP-METRIC-1"}
     for k, v in res["mean"].items():
@@ -197,4 +217,9 @@ def report(res, ref_path, dist_path, per_frame=False):
             for name in PLANES + ("all",):
                 key = "%s_%s" % (kind, name)
                 out[key + "_frames"] = [json_value(v) for v in res[key]]
+        if "ms_ssim_y" in res:
+            for key in ("ms_ssim_y", "ssim_gauss_y"):
+                out[key + "_frames"] = [json_value(v) for v in res[key]]
+            for key in ("cs_scales_y", "ssim_scales_y"):
+                out[key + "_frames"] = [[json_value(v) for v in row] for row in res[key]]
     return out
