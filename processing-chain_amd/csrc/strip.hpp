@@ -50,6 +50,11 @@ template <int HW, int SB>
 constexpr int strip_pf() {
     return HW >= 8 ? (SB == 2 ? PIXPATH_STRIP_PF_WIDE : PIXPATH_STRIP_PF_U8_WIDE) : PIXPATH_STRIP_PF_NARROW;
 }
+// V pass: skip a row's zero last tap pair (0 = every row runs all VT pairs;
+// config 2: 1.492 -> 1.410 ms per launch, profiles/r7)
+#ifndef PIXPATH_STRIP_VSKIP
+#define PIXPATH_STRIP_VSKIP 1
+#endif
 template <int PF>
 struct StripPrefetch {
     uint4 v[PF];
@@ -548,9 +553,18 @@ __global__ __launch_bounds__(TW, (FUSE >= 8 ? strip_fused_min_waves<HW, VTM, FUS
                     const int y = y0 + yy;
                     uint8_t *drow_p = dbase + (int64_t)y * dls;
                     const uint4 *rp = reinterpret_cast<const uint4 *>(win + ((vb[i] - nbase) >> 1) * TW + vx);
+                    // VSKIP (plain plans, 3+ tap pairs): a row whose taps start on
+                    // an even source row leaves its last pair zero (a third of
+                    // config 2's rows); that pair's window read and 4 v_dot2 run
+                    // only where the record has taps in it.  The record is in
+                    // SGPRs, so this is a scalar branch; the read sits with its
+                    // v_dot2 behind the other pairs' math (hoisted beside their
+                    // reads it spilled a VGPR; a chain instance spills with the skip)
+                    constexpr bool VSKIP = PIXPATH_STRIP_VSKIP && VT >= 3 && FUSE == 0;
+                    constexpr int VTU = VT - (VSKIP ? 1 : 0);  // pairs every row reads
                     uint4 q[VT];
 #pragma unroll
-                    for (int j = 0; j < VT; ++j) q[j] = rp[j * (TW / 4)];
+                    for (int j = 0; j < VTU; ++j) q[j] = rp[j * (TW / 4)];
                     int acc[4];
                     // the first tap pair onto the rounding constant (16-bit rows)
                     // or the row's dither init (8-bit rows), both VGPRs
@@ -581,13 +595,21 @@ __global__ __launch_bounds__(TW, (FUSE >= 8 ? strip_fused_min_waves<HW, VTM, FUS
                         acc[2] = dot2_sv(__builtin_bit_cast(v2i16, q[0].z), cf[i][0], kround);
                         acc[3] = dot2_sv(__builtin_bit_cast(v2i16, q[0].w), cf[i][0], kround);
                     }
-#pragma unroll
-                    for (int j = 1; j < VT; ++j) {
+                    auto vtap = [&](int j) {
                         const v2i16 c2 = __builtin_bit_cast(v2i16, cf[i][j]);
                         acc[0] = __builtin_amdgcn_sdot2(__builtin_bit_cast(v2i16, q[j].x), c2, acc[0], false);
                         acc[1] = __builtin_amdgcn_sdot2(__builtin_bit_cast(v2i16, q[j].y), c2, acc[1], false);
                         acc[2] = __builtin_amdgcn_sdot2(__builtin_bit_cast(v2i16, q[j].z), c2, acc[2], false);
                         acc[3] = __builtin_amdgcn_sdot2(__builtin_bit_cast(v2i16, q[j].w), c2, acc[3], false);
+                    };
+#pragma unroll
+                    for (int j = 1; j < VTU; ++j) vtap(j);
+                    if constexpr (VSKIP) {
+                        if (cf[i][VT - 1] != 0) {
+                            asm volatile("");  // keeps the branch: not 4 v_dot2 and 4 selects
+                            q[VT - 1] = rp[(VT - 1) * (TW / 4)];
+                            vtap(VT - 1);
+                        }
                     }
                     if ((!CL && !lane_any) || (PP_ABLATE(a.debug) & 1)) continue;
                     constexpr int sh = OUTB == 8 ? 19 : 11 + 16 - OUTB;
