@@ -488,6 +488,49 @@ int pp_ms_ssim(pp_ctx *ctx, int bitdepth, int w, int h,
                const void *dist, int64_t dist_linesize, int64_t dist_frame_stride, int ndist,
                const int32_t *ref_index, double *out, void *stream);
 
+/* ---- pixel-domain VIF of a distorted luma batch against its reference
+ * (spec PP-VIF-1) ---------------------------------------------
+ * Visual Information Fidelity after Sheikh & Bovik 2006 in the four-scale
+ * pixel-domain form VMAF uses as vif_scale0..3.  Samples are brought to the
+ * 8-bit scale (sample / 2^(bitdepth - 8), exact); scale s = 0 .. 3 has
+ * w >> s x h >> s samples and a Gaussian window of 17, 9, 5, 3 taps (sigma =
+ * taps / 5, normalised in fp64); scale s + 1 is scale s under the window of
+ * scale s + 1, even rows and columns kept.  Borders are mirrored without
+ * repeating the edge sample on all four sides, so every sample position of a
+ * scale has a window.  A scale exists if it is at least taps / 2 + 1 samples
+ * wide and high (9, 5, 3, 2; all four from 16 x 16 on).  ref, dist, bitdepth,
+ * ref_index and their rules are pp_ms_ssim's: bitdepth 8 is bytes, 10 is
+ * uint16 LE taken as stored, nothing masked; dist frame k is compared with ref
+ * frame ref_index[k] (HOST array of ndist entries, NULL = identity, which needs
+ * ndist <= nref; an entry outside [0, nref) is PP_ERR_INVALID).
+ *   out [ndist][4][2] double, DEVICE, every element written and nothing else:
+ *        out[k][s][0] = sum of num, out[k][s][1] = sum of den over the
+ *        (w >> s)(h >> s) positions of scale s (sigma_n^2 = 2, eps = 1e-10, the
+ *        steps of DESIGN.md in order); both NaN for a scale that does not exist
+ *        and for every later one.
+ * vif_scale_s = num_s / den_s and vif = sum num / sum den are host arithmetic:
+ * pixpath/vif.py `pool`.  Everything is fp64.  Identical planes give values
+ * within 1e-9 of 1 where sigma_1^2 >= 2 everywhere, not exactly 1: eps keeps
+ * the gain just under 1.  Two runs give the same bits (no atomics, partials
+ * added in a fixed order).  Pitch padding never counts.  NULL ctx, ref, dist or
+ * out, w or h < 1, ndist or nref < 0, a linesize below the row's bytes, 16-bit
+ * samples off the 2-byte grid and a bitdepth other than 8 or 10 are
+ * PP_ERR_INVALID; a plane past the 2 GiB buffer range is PP_ERR_UNSUPPORTED.
+ * Arguments are checked before any HIP call; ndist == 0 is PP_OK and writes
+ * nothing.  Every sample is loaded as one element at a mirrored position,
+ * whatever grid the pointers, linesizes and frame strides lie on: the layout of
+ * the same samples cannot change a bit of the result.  The workspace (fp64
+ * pyramid levels 1 .. 3 of both planes of up to 256 frames or 1 GiB a launch,
+ * about 11 MB a frame at 1080p, and one partial per frame, scale and tile of
+ * 256 x 64 positions) belongs to the context.  The constants are those
+ * published for VMAF's VIF feature; parity with libvmaf's float_vif is
+ * unpinned: no libvmaf exists to compare with, and its border and decimation
+ * details could not be read.  Added without raising PP_ABI_VERSION (still 7). */
+int pp_vif(pp_ctx *ctx, int bitdepth, int w, int h,
+           const void *ref, int64_t ref_linesize, int64_t ref_frame_stride, int nref,
+           const void *dist, int64_t dist_linesize, int64_t dist_frame_stride, int ndist,
+           const int32_t *ref_index, double *out, void *stream);
+
 /* ---- host helpers --------------------------------------------------------
  * vf_fps output->input frame map (lib/ffmpeg.py:832-834, :959-961, :1038,
  * :1179): map[k] = input frame shown at output frame k.  Returns the number of

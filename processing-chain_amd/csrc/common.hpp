@@ -117,9 +117,9 @@ struct Ctx {
     void *spin_buf = nullptr; // [n][Y(w*h) A(w*h) U V Ac (cw*ch each)] uint16
     // partials of pp_metrics (PP-METRIC-1) and pp_frame_adler32 (PP-HASH-1), tile
     // histograms of pp_frame_stats (PP-STATS-1), partials of pp_frame_sse_band
-    // (PP-ALIGN-1), pyramids and partials of pp_ms_ssim (PP-MSSSIM-1).  One each:
-    // the five may be enqueued on different streams at once.
-    Scratch met, crc, stat, aln, mss;
+    // (PP-ALIGN-1), pyramids and partials of pp_ms_ssim (PP-MSSSIM-1) and of pp_vif
+    // (PP-VIF-1).  One each: the six may be enqueued on different streams at once.
+    Scratch met, crc, stat, aln, mss, vif;
 };
 
 } // namespace pp

@@ -32,7 +32,7 @@ def _psnr(mse, peak):
     return out
 
 
-def summarize(sse, ssim, fmt, w, h, matched=None, ms_terms=None):
+def summarize(sse, ssim, fmt, w, h, matched=None, ms_terms=None, vif_terms=None):
     """Host side of PP-METRIC-1: per-frame arrays ``mse_y/u/v/all``,
     ``psnr_y/u/v/all``, ``ssim_y/u/v/all`` (float64 [N]) from pp_metrics' sums
     (sse [N, 3] integers, ssim [N, 3]), plus ``mean``: the clip values (mean
@@ -44,7 +44,9 @@ def summarize(sse, ssim, fmt, w, h, matched=None, ms_terms=None):
     out.  ``ms_terms`` (pp_ms_ssim's [N, 5, 2], spec PP-MSSSIM-1; only when
     asked for): adds ``ms_ssim_y``, ``ssim_gauss_y`` [N], ``cs_scales_y`` and
     ``ssim_scales_y`` [N, 5] and the clip means of the first two
-    (msssim.summarize)."""
+    (msssim.summarize).  ``vif_terms`` (pp_vif's [N, 4, 2], spec PP-VIF-1; only
+    when asked for): adds ``vif_y`` [N] and ``vif_scales_y`` [N, 4] and their
+    clip means (vif.summarize)."""
     f = formats.fmt(fmt)
     sse = np.asarray(sse).reshape(-1, 3)
     ssim = np.asarray(ssim, dtype=np.float64).reshape(-1, 3)
@@ -84,6 +86,11 @@ def summarize(sse, ssim, fmt, w, h, matched=None, ms_terms=None):
         ms = msssim.summarize(ms_terms, matched)
         mean.update(ms.pop("mean"))
         res.update(ms)
+    if vif_terms is not None:
+        from . import vif
+        vs = vif.summarize(vif_terms, matched)
+        mean.update(vs.pop("mean"))
+        res.update(vs)
     return res
 
 
@@ -99,7 +106,7 @@ def _map_entries(k0, n, in_rate, out_rate, n_in=None):
 
 
 def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, crop_from="yuv422p", ref_index=None,
-                     ms_ssim=False):
+                     ms_ssim=False, vif=False):
     """PP-METRIC-1 of the file ``dist_path`` (the PVS) against ``ref_path``
     (the SRC); returns ``summarize``'s dict.  Both are read with the chain's
     own readers (FFV1 AVIs through ffv1.open_avpvs_reader, anything else
@@ -126,7 +133,10 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, 
     distorted clip and the map.
 
     ``ms_ssim``: also the luma MS-SSIM and Gaussian-window SSIM of every frame
-    pair (spec PP-MSSSIM-1, ops.ms_ssim on the same resident frames)."""
+    pair (spec PP-MSSSIM-1, ops.ms_ssim on the same resident frames).
+
+    ``vif``: also the luma VIF and its four per-scale values of every frame
+    pair (spec PP-VIF-1, ops.vif on the same resident frames)."""
     import torch
 
     from . import ops
@@ -141,7 +151,7 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, 
         scaler = None if same else ops.Scaler(rfmt, ref.w, ref.h, dfmt, dw, dh, flags=flags, device=dev)
         in_rate, out_rate = ref.rate, dist.rate
         win, win0, n_ref, ref_end = None, 0, 0, False  # resident reference frames [win0, n_ref), dist geometry
-        outs, terms, k0 = [], [], 0
+        outs, terms, vterms, k0 = [], [], [], 0
         explicit = None if ref_index is None else np.asarray(ref_index, dtype=np.int64).reshape(-1)
         last = 0  # explicit map: the reference frame an unmatched distorted frame is read against (and not reported)
         for d in dists:
@@ -187,6 +197,8 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, 
             outs.append(ops.metrics(win, d, ref_index=m - win0))
             if ms_ssim:
                 terms.append(ops.ms_ssim(win, d, ref_index=m - win0))
+            if vif:
+                vterms.append(ops.vif(win, d, ref_index=m - win0))
             k0 += d.n
         torch.cuda.current_stream(dev).synchronize()
     if outs:
@@ -197,9 +209,12 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, 
     ms = None
     if ms_ssim:
         ms = torch.cat(terms).cpu().numpy() if terms else np.zeros((0, 5, 2))
+    vt = None
+    if vif:
+        vt = torch.cat(vterms).cpu().numpy() if vterms else np.zeros((0, 4, 2))
     if explicit is None:
-        return summarize(sse, ssim, dfmt, dw, dh, ms_terms=ms)
-    return summarize(sse, ssim, dfmt, dw, dh, matched=explicit[:sse.shape[0]] >= 0, ms_terms=ms)
+        return summarize(sse, ssim, dfmt, dw, dh, ms_terms=ms, vif_terms=vt)
+    return summarize(sse, ssim, dfmt, dw, dh, matched=explicit[:sse.shape[0]] >= 0, ms_terms=ms, vif_terms=vt)
 
 
 def report(res, ref_path, dist_path, per_frame=False):
@@ -207,11 +222,13 @@ def report(res, ref_path, dist_path, per_frame=False):
     the per-frame lists; NaN and infinite values become null.  A result with
     MS-SSIM (summarize's ms_terms) adds ``ms_ssim_y``, ``ssim_gauss_y`` and,
     per frame, those two and the per-scale means ``cs_scales_y_frames`` /
-    ``ssim_scales_y_frames`` ([N][5])."""
+    ``ssim_scales_y_frames`` ([N][5]).  A result with VIF (summarize's
+    vif_terms) adds ``vif_y`` and ``vif_scales_y`` (four values) and, per
+    frame, ``vif_y_frames`` and ``vif_scales_y_frames`` ([N][4])."""
     out = {"ref": os.path.basename(ref_path), "file": os.path.basename(dist_path), "frames": int(res["frames"]),
            "spec": "PP-METRIC-1"}
     for k, v in res["mean"].items():
-        out[k] = json_value(v)
+        out[k] = [json_value(x) for x in v] if isinstance(v, list) else json_value(v)
     if per_frame:
         for kind in ("mse", "psnr", "ssim"):
             for name in PLANES + ("all",):
@@ -222,4 +239,7 @@ def report(res, ref_path, dist_path, per_frame=False):
                 out[key + "_frames"] = [json_value(v) for v in res[key]]
             for key in ("cs_scales_y", "ssim_scales_y"):
                 out[key + "_frames"] = [[json_value(v) for v in row] for row in res[key]]
+        if "vif_y" in res:
+            out["vif_y_frames"] = [json_value(v) for v in res["vif_y"]]
+            out["vif_scales_y_frames"] = [[json_value(v) for v in row] for row in res["vif_scales_y"]]
     return out
