@@ -531,6 +531,54 @@ int pp_vif(pp_ctx *ctx, int bitdepth, int w, int h,
            const void *dist, int64_t dist_linesize, int64_t dist_frame_stride, int ndist,
            const int32_t *ref_index, double *out, void *stream);
 
+/* ---- Additive / Detail-loss Metric of a distorted luma batch against its
+ * reference (spec PP-ADM-1) -----------------------------------
+ * ADM after Li, Ngan et al. 2011 in the four-scale form VMAF uses as adm2 and
+ * adm_scale0..3.  Samples are brought to the 8-bit scale (sample /
+ * 2^(bitdepth - 8), exact).  Level s = 0 .. 3 of the Daubechies-2 transform has
+ * (w_{s-1} + 1) / 2 x (h_{s-1} + 1) / 2 coefficients (level -1: the plane);
+ * coefficient i of an axis reads inputs 2i - 1 .. 2i + 2 under the low-pass or
+ * high-pass taps, borders mirrored without repeating the edge sample; rows are
+ * filtered first, then columns; level s + 1 is taken from the approximation
+ * band of level s.  Per position the distorted H, V, D coefficients are
+ * decoupled into a restored and an additive part (gain clipped to [0, 1]; both
+ * directions within one degree: all restored), weighted by the contrast
+ * sensitivity rf[s][theta], and the restored part is lowered by the masking
+ * threshold M taken from the additive part's 3 x 3 neighbourhood.  A scale
+ * exists if its input and its bands are at least 3 samples wide and high (all
+ * four from 33 x 33 on).  ref, dist, bitdepth, ref_index and their rules are
+ * pp_vif's: bitdepth 8 is bytes, 10 is uint16 LE taken as stored, nothing
+ * masked; dist frame k is compared with ref frame ref_index[k] (HOST array of
+ * ndist entries, NULL = identity, which needs ndist <= nref; an entry outside
+ * [0, nref) is PP_ERR_INVALID).
+ *   out [ndist][4][6] double, DEVICE, every element written and nothing else:
+ *        out[k][s][0..2] = sum of max(|rf r| - M, 0)^3 for H, V, D and
+ *        out[k][s][3..5] = sum of |rf o|^3 for H, V, D over the region of scale
+ *        s (the band less a margin of max(1, (n - 5) / 10) on every side); all
+ *        six NaN for a scale that does not exist and for every later one.
+ * adm_scale_s and adm2 are host arithmetic: pixpath/adm.py `pool`.  Everything
+ * is fp64.  Identical planes give the same bits in out[k][s][i] and
+ * out[k][s][3 + i], so every pooled value is exactly 1.0.  Two runs give the
+ * same bits (no atomics, partials added in a fixed order).  Pitch padding never
+ * counts.  NULL ctx, ref, dist or out, w or h < 1, ndist or nref < 0, a
+ * linesize below the row's bytes, 16-bit samples off the 2-byte grid and a
+ * bitdepth other than 8 or 10 are PP_ERR_INVALID; a plane past the 2 GiB
+ * buffer range is PP_ERR_UNSUPPORTED.  Arguments are checked before any HIP
+ * call; ndist == 0 is PP_OK and writes nothing.  Every sample is loaded as one
+ * element at a mirrored position, whatever grid the pointers, linesizes and
+ * frame strides lie on: the layout of the same samples cannot change a bit of
+ * the result.  The workspace (fp64 approximation bands of levels 0 .. 2 of
+ * both planes of up to 256 frames or 1 GiB a launch, about 11 MB a frame at
+ * 1080p, and one partial per frame, scale and tile of 254 x 32 coefficients)
+ * belongs to the context; the H, V and D bands are never stored.  The
+ * constants are those published for VMAF's ADM feature; parity with libvmaf's
+ * float_adm is unpinned: no libvmaf exists to compare with.  Added without
+ * raising PP_ABI_VERSION (still 7). */
+int pp_adm(pp_ctx *ctx, int bitdepth, int w, int h,
+           const void *ref, int64_t ref_linesize, int64_t ref_frame_stride, int nref,
+           const void *dist, int64_t dist_linesize, int64_t dist_frame_stride, int ndist,
+           const int32_t *ref_index, double *out, void *stream);
+
 /* ---- host helpers --------------------------------------------------------
  * vf_fps output->input frame map (lib/ffmpeg.py:832-834, :959-961, :1038,
  * :1179): map[k] = input frame shown at output frame k.  Returns the number of

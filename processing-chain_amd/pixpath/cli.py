@@ -16,7 +16,8 @@ the ffmpeg strings they replace).
   metrics per-frame PSNR / SSIM of a PVS against its SRC (spec PP-METRIC-1; after p03);
           --crop WxH [--avpvs-pix-fmt NAME] scores a v210 / UYVY CPVS against its AVPVS;
           --ms-ssim adds the luma MS-SSIM and Gaussian-window SSIM (spec PP-MSSSIM-1);
-          --vif adds the luma VIF and its four per-scale values (spec PP-VIF-1)
+          --vif adds the luma VIF and its four per-scale values (spec PP-VIF-1);
+          --adm adds the luma ADM (adm2) and its four per-scale values (spec PP-ADM-1)
   framecrc FFmpeg's `-f framecrc` listing of a file: one GPU Adler-32 per frame (spec PP-HASH-1);
           --against FILE compares with a listing; `avpvs --framecrc FILE` lists what the writer was given
   stats  what is inside one clip (spec PP-STATS-1): per-plane range, mean, percentiles, used bits,
@@ -671,6 +672,8 @@ def cmd_metrics(args):
         kw["ms_ssim"] = True
     if args.vif:  # luma VIF and its four per-scale values as well (spec PP-VIF-1)
         kw["vif"] = True
+    if args.adm:  # luma ADM and its four per-scale values as well (spec PP-ADM-1)
+        kw["adm"] = True
     res = metrics.metrics_of_files(args.ref, args.input, batch=args.batch, flags=args.flags, **kw)
     out = metrics.report(res, args.ref, args.input, per_frame=args.per_frame)
     out.update(extra)
@@ -857,6 +860,8 @@ def main(argv=None):
                    help="add the luma MS-SSIM and Gaussian-window SSIM (spec PP-MSSSIM-1)")
     p.add_argument("--vif", action="store_true",
                    help="add the luma VIF and its four per-scale values (spec PP-VIF-1)")
+    p.add_argument("--adm", action="store_true",
+                   help="add the luma ADM (adm2) and its four per-scale values (spec PP-ADM-1)")
     p.set_defaults(fn=cmd_metrics)
 
     p = sub.add_parser("align")

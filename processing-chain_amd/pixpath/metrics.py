@@ -32,7 +32,7 @@ def _psnr(mse, peak):
     return out
 
 
-def summarize(sse, ssim, fmt, w, h, matched=None, ms_terms=None, vif_terms=None):
+def summarize(sse, ssim, fmt, w, h, matched=None, ms_terms=None, vif_terms=None, adm_terms=None):
     """Host side of PP-METRIC-1: per-frame arrays ``mse_y/u/v/all``,
     ``psnr_y/u/v/all``, ``ssim_y/u/v/all`` (float64 [N]) from pp_metrics' sums
     (sse [N, 3] integers, ssim [N, 3]), plus ``mean``: the clip values (mean
@@ -46,7 +46,9 @@ def summarize(sse, ssim, fmt, w, h, matched=None, ms_terms=None, vif_terms=None)
     ``ssim_scales_y`` [N, 5] and the clip means of the first two
     (msssim.summarize).  ``vif_terms`` (pp_vif's [N, 4, 2], spec PP-VIF-1; only
     when asked for): adds ``vif_y`` [N] and ``vif_scales_y`` [N, 4] and their
-    clip means (vif.summarize)."""
+    clip means (vif.summarize).  ``adm_terms`` (pp_adm's [N, 4, 6], spec
+    PP-ADM-1; only when asked for): adds ``adm2_y`` [N] and ``adm_scales_y``
+    [N, 4] and their clip means (adm.summarize)."""
     f = formats.fmt(fmt)
     sse = np.asarray(sse).reshape(-1, 3)
     ssim = np.asarray(ssim, dtype=np.float64).reshape(-1, 3)
@@ -91,6 +93,11 @@ def summarize(sse, ssim, fmt, w, h, matched=None, ms_terms=None, vif_terms=None)
         vs = vif.summarize(vif_terms, matched)
         mean.update(vs.pop("mean"))
         res.update(vs)
+    if adm_terms is not None:
+        from . import adm
+        ad = adm.summarize(adm_terms, w, h, matched)
+        mean.update(ad.pop("mean"))
+        res.update(ad)
     return res
 
 
@@ -106,7 +113,7 @@ def _map_entries(k0, n, in_rate, out_rate, n_in=None):
 
 
 def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, crop_from="yuv422p", ref_index=None,
-                     ms_ssim=False, vif=False):
+                     ms_ssim=False, vif=False, adm=False):
     """PP-METRIC-1 of the file ``dist_path`` (the PVS) against ``ref_path``
     (the SRC); returns ``summarize``'s dict.  Both are read with the chain's
     own readers (FFV1 AVIs through ffv1.open_avpvs_reader, anything else
@@ -136,7 +143,10 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, 
     pair (spec PP-MSSSIM-1, ops.ms_ssim on the same resident frames).
 
     ``vif``: also the luma VIF and its four per-scale values of every frame
-    pair (spec PP-VIF-1, ops.vif on the same resident frames)."""
+    pair (spec PP-VIF-1, ops.vif on the same resident frames).
+
+    ``adm``: also the luma ADM (adm2) and its four per-scale values of every
+    frame pair (spec PP-ADM-1, ops.adm on the same resident frames)."""
     import torch
 
     from . import ops
@@ -151,7 +161,7 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, 
         scaler = None if same else ops.Scaler(rfmt, ref.w, ref.h, dfmt, dw, dh, flags=flags, device=dev)
         in_rate, out_rate = ref.rate, dist.rate
         win, win0, n_ref, ref_end = None, 0, 0, False  # resident reference frames [win0, n_ref), dist geometry
-        outs, terms, vterms, k0 = [], [], [], 0
+        outs, terms, vterms, aterms, k0 = [], [], [], [], 0
         explicit = None if ref_index is None else np.asarray(ref_index, dtype=np.int64).reshape(-1)
         last = 0  # explicit map: the reference frame an unmatched distorted frame is read against (and not reported)
         for d in dists:
@@ -199,6 +209,8 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, 
                 terms.append(ops.ms_ssim(win, d, ref_index=m - win0))
             if vif:
                 vterms.append(ops.vif(win, d, ref_index=m - win0))
+            if adm:
+                aterms.append(ops.adm(win, d, ref_index=m - win0))
             k0 += d.n
         torch.cuda.current_stream(dev).synchronize()
     if outs:
@@ -212,9 +224,13 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, 
     vt = None
     if vif:
         vt = torch.cat(vterms).cpu().numpy() if vterms else np.zeros((0, 4, 2))
+    at = None
+    if adm:
+        at = torch.cat(aterms).cpu().numpy() if aterms else np.zeros((0, 4, 6))
     if explicit is None:
-        return summarize(sse, ssim, dfmt, dw, dh, ms_terms=ms, vif_terms=vt)
-    return summarize(sse, ssim, dfmt, dw, dh, matched=explicit[:sse.shape[0]] >= 0, ms_terms=ms, vif_terms=vt)
+        return summarize(sse, ssim, dfmt, dw, dh, ms_terms=ms, vif_terms=vt, adm_terms=at)
+    return summarize(sse, ssim, dfmt, dw, dh, matched=explicit[:sse.shape[0]] >= 0, ms_terms=ms, vif_terms=vt,
+                     adm_terms=at)
 
 
 def report(res, ref_path, dist_path, per_frame=False):
@@ -224,7 +240,10 @@ def report(res, ref_path, dist_path, per_frame=False):
     per frame, those two and the per-scale means ``cs_scales_y_frames`` /
     ``ssim_scales_y_frames`` ([N][5]).  A result with VIF (summarize's
     vif_terms) adds ``vif_y`` and ``vif_scales_y`` (four values) and, per
-    frame, ``vif_y_frames`` and ``vif_scales_y_frames`` ([N][4])."""
+    frame, ``vif_y_frames`` and ``vif_scales_y_frames`` ([N][4]).  A result
+    with ADM (summarize's adm_terms) adds ``adm2_y`` and ``adm_scales_y`` (four
+    values) and, per frame, ``adm2_y_frames`` and ``adm_scales_y_frames``
+    ([N][4])."""
     out = {"ref": os.path.basename(ref_path), "file": os.path.basename(dist_path), "frames": int(res["frames"]),
            "spec": "PP-METRIC-1"}
     for k, v in res["mean"].items():
@@ -242,4 +261,7 @@ def report(res, ref_path, dist_path, per_frame=False):
         if "vif_y" in res:
             out["vif_y_frames"] = [json_value(v) for v in res["vif_y"]]
             out["vif_scales_y_frames"] = [[json_value(v) for v in row] for row in res["vif_scales_y"]]
+        if "adm2_y" in res:
+            out["adm2_y_frames"] = [json_value(v) for v in res["adm2_y"]]
+            out["adm_scales_y_frames"] = [[json_value(v) for v in row] for row in res["adm_scales_y"]]
     return out

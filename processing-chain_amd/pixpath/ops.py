@@ -492,6 +492,41 @@ def vif(ref_batch, dist_batch, ref_index=None, stream=None):
     return out
 
 
+def adm(ref_batch, dist_batch, ref_index=None, stream=None):
+    """Per-scale ADM sums of every frame of ``dist_batch`` against ``ref_batch``
+    (spec PP-ADM-1, pp_adm): two FrameBatches of one size and bit depth, or
+    their [N, H, W] luma tensors (any pitches).  Distorted frame k is compared
+    with reference frame ``ref_index[k]`` (default: k).  Returns a device
+    tensor float64 [ndist, 4, 6] on the current stream: out[k, s, 0:3] the sums
+    of the cubed masked restored coefficients of H, V, D and out[k, s, 3:6] the
+    sums of the cubed weighted reference coefficients over the region of scale
+    s, NaN for a scale that does not exist.  pixpath.adm.pool turns it into
+    adm_scale0..3 and adm2."""
+    r, rd = _luma(ref_batch)
+    d, dd = _luma(dist_batch)
+    if rd != dd or tuple(r.shape[1:]) != tuple(d.shape[1:]):
+        raise ValueError("ref and dist differ in bit depth or size")
+    if r.device != d.device:
+        raise ValueError("ref and dist are on different devices")
+    n, h, w = d.shape
+    idx = None
+    if ref_index is not None:
+        idx = np.ascontiguousarray(ref_index, dtype=np.int32)
+        if idx.shape != (n,):
+            raise ValueError("ref_index needs one entry per dist frame")
+    out = torch.empty((n, 4, 6), dtype=torch.float64, device=d.device)
+    if n == 0:  # an empty batch has no data pointer to pass
+        return out
+    es = d.element_size()
+    ctx = context(d.device.index)
+    rp = r.data_ptr() if r.shape[0] else d.data_ptr()  # an empty reference: the call rejects the map
+    check(lib().pp_adm(ctx.handle, dd, w, h, ctypes.c_void_p(rp), r.stride(1) * es, r.stride(0) * es, r.shape[0],
+                       ctypes.c_void_p(d.data_ptr()), d.stride(1) * es, d.stride(0) * es, n,
+                       None if idx is None else idx.ctypes.data, ctypes.c_void_p(out.data_ptr()),
+                       _stream(d, stream)))
+    return out
+
+
 def spinner_upload(rgba_frames, f, device=None):
     """Upload an RGBA8 animation [n, h, w, 4] (host) for stall compositing."""
     a = np.ascontiguousarray(rgba_frames, dtype=np.uint8)
