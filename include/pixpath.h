@@ -579,6 +579,51 @@ int pp_adm(pp_ctx *ctx, int bitdepth, int w, int h,
            const void *dist, int64_t dist_linesize, int64_t dist_frame_stride, int ndist,
            const int32_t *ref_index, double *out, void *stream);
 
+/* ---- VMAF-style motion of a luma sequence (spec PP-MOTION-1) --
+ * The temporal feature VMAF calls motion / motion2: every shown frame's luma
+ * is blurred with the separable integer filter f = {3571, 16004, 26386, 16004,
+ * 3571} (sum 65536), columns first, a rounding after each pass:
+ *   t(i, j) = (sum_k f[k] x(m(i + k - 2, h), j) + 2^(d-1)) >> d
+ *   B(i, j) = (sum_k f[k] t(i, m(j + k - 2, w)) + 32768) >> 16
+ * with d = bitdepth and m mirroring without repeating the edge sample
+ * (PP-VIF-1's rule).  bitdepth 8 is bytes, 10 is uint16 LE; unlike the
+ * comparison metrics a stored sample above 2^d - 1 counts as 2^d - 1 (x =
+ * min(stored, 2^d - 1)): that keeps every intermediate below 2^32 and B in 16
+ * bits (B <= 65472).  A constant plane c gives B = c 2^(16-d) exactly.  The
+ * shown sequence is src[index[0]], .., src[index[n-1]] (index: HOST array of n
+ * entries, NULL = identity, which needs n <= nsrc; an entry outside [0, nsrc)
+ * is PP_ERR_INVALID; repeats and backward steps are allowed, a repeat gives
+ * exactly 0).
+ *   sad [n] uint64, DEVICE, every element written and nothing else:
+ *        sad[k] = sum over the plane of |B(src[index[k]]) - B(src[index[k-1]])|,
+ *        exact, < 2^47; sad[0] is taken against `prev` (one luma plane of the
+ *        same w, h and bitdepth, pitch prev_linesize), or is UINT64_MAX =
+ *        absent when prev is NULL (as pp_frame_stats' sad); with w < 3 or
+ *        h < 3 one reflection does not suffice and every entry is absent.
+ * motion = sad / 256 / (w h) (the 8-bit scale at both depths) and motion2 are
+ * host arithmetic: pixpath/motion.py `pool`.  Everything is 32-bit unsigned
+ * integer arithmetic, 64-bit from the tile's sum up: no float, no atomics,
+ * partials added in a fixed order, two runs give the same bits.  Pitch padding
+ * never counts.  NULL ctx, src or sad, w or h < 1, n or nsrc < 0, a linesize
+ * below the row's bytes, 16-bit samples off the 2-byte grid and a bitdepth
+ * other than 8 or 10 are PP_ERR_INVALID; a plane past the 2 GiB buffer range
+ * is PP_ERR_UNSUPPORTED.  Arguments are checked before any HIP call; n == 0 is
+ * PP_OK and writes nothing.  Pointers, linesizes and the frame stride on the
+ * 16-B grid take 16-B loads, anything else element loads with the same
+ * results.  A workgroup walks a segment of 4 shown frames over its tile with
+ * the previous frame's blurred tile in registers: no blurred sample is ever
+ * stored, and the workspace (one 64-bit partial per frame and tile of 64 rows
+ * x 62 16-B pieces, up to 256 frames a launch) belongs to the context.  The
+ * taps, the two roundings and the / 256 are libvmaf's integer motion as
+ * recalled, the mirror rule is this library's; parity with libvmaf is
+ * unpinned: no libvmaf exists to compare with.  Added without raising
+ * PP_ABI_VERSION (still 7). */
+int pp_motion(pp_ctx *ctx, int bitdepth, int w, int h,
+              const void *src, int64_t src_linesize, int64_t src_frame_stride, int nsrc,
+              const int32_t *index, int n,
+              const void *prev, int64_t prev_linesize,
+              uint64_t *sad, void *stream);
+
 /* ---- host helpers --------------------------------------------------------
  * vf_fps output->input frame map (lib/ffmpeg.py:832-834, :959-961, :1038,
  * :1179): map[k] = input frame shown at output frame k.  Returns the number of

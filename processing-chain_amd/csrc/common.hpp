@@ -118,9 +118,10 @@ struct Ctx {
     // partials of pp_metrics (PP-METRIC-1) and pp_frame_adler32 (PP-HASH-1), tile
     // histograms of pp_frame_stats (PP-STATS-1), partials of pp_frame_sse_band
     // (PP-ALIGN-1), pyramids and partials of pp_ms_ssim (PP-MSSSIM-1) and of pp_vif
-    // (PP-VIF-1), approximation bands and partials of pp_adm (PP-ADM-1).  One each:
-    // the seven may be enqueued on different streams at once.
-    Scratch met, crc, stat, aln, mss, vif, adm;
+    // (PP-VIF-1), approximation bands and partials of pp_adm (PP-ADM-1), partials of
+    // pp_motion (PP-MOTION-1).  One each: the eight may be enqueued on different
+    // streams at once.
+    Scratch met, crc, stat, aln, mss, vif, adm, mot;
 };
 
 } // namespace pp

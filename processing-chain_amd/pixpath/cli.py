@@ -17,7 +17,9 @@ the ffmpeg strings they replace).
           --crop WxH [--avpvs-pix-fmt NAME] scores a v210 / UYVY CPVS against its AVPVS;
           --ms-ssim adds the luma MS-SSIM and Gaussian-window SSIM (spec PP-MSSSIM-1);
           --vif adds the luma VIF and its four per-scale values (spec PP-VIF-1);
-          --adm adds the luma ADM (adm2) and its four per-scale values (spec PP-ADM-1)
+          --adm adds the luma ADM (adm2) and its four per-scale values (spec PP-ADM-1);
+          --motion adds motion and motion2 of the reference frames as shown (spec PP-MOTION-1);
+          --vmaf-features implies the three and adds the six-value feature vector a VMAF model takes
   framecrc FFmpeg's `-f framecrc` listing of a file: one GPU Adler-32 per frame (spec PP-HASH-1);
           --against FILE compares with a listing; `avpvs --framecrc FILE` lists what the writer was given
   stats  what is inside one clip (spec PP-STATS-1): per-plane range, mean, percentiles, used bits,
@@ -674,8 +676,14 @@ def cmd_metrics(args):
         kw["vif"] = True
     if args.adm:  # luma ADM and its four per-scale values as well (spec PP-ADM-1)
         kw["adm"] = True
+    if args.motion:  # motion and motion2 of the reference frames as shown as well (spec PP-MOTION-1)
+        kw["motion"] = True
+    if args.vmaf_features:  # the six elementary features of the published VMAF models; no model is applied
+        kw.update(vif=True, adm=True, motion=True)
     res = metrics.metrics_of_files(args.ref, args.input, batch=args.batch, flags=args.flags, **kw)
     out = metrics.report(res, args.ref, args.input, per_frame=args.per_frame)
+    if args.vmaf_features:
+        out.update(metrics.vmaf_features(res, per_frame=args.per_frame))
     out.update(extra)
     print(json.dumps(out))
     return 0
@@ -862,6 +870,11 @@ def main(argv=None):
                    help="add the luma VIF and its four per-scale values (spec PP-VIF-1)")
     p.add_argument("--adm", action="store_true",
                    help="add the luma ADM (adm2) and its four per-scale values (spec PP-ADM-1)")
+    p.add_argument("--motion", action="store_true",
+                   help="add motion and motion2 of the reference frames as shown (spec PP-MOTION-1)")
+    p.add_argument("--vmaf-features", action="store_true",
+                   help="implies --vif --adm --motion; add the feature vector adm2, motion2, vif_scale0..3 "
+                        "(vmaf_features, vmaf_feature_names; with --per-frame vmaf_features_frames)")
     p.set_defaults(fn=cmd_metrics)
 
     p = sub.add_parser("align")

@@ -32,7 +32,8 @@ def _psnr(mse, peak):
     return out
 
 
-def summarize(sse, ssim, fmt, w, h, matched=None, ms_terms=None, vif_terms=None, adm_terms=None):
+def summarize(sse, ssim, fmt, w, h, matched=None, ms_terms=None, vif_terms=None, adm_terms=None,
+              motion_terms=None):
     """Host side of PP-METRIC-1: per-frame arrays ``mse_y/u/v/all``,
     ``psnr_y/u/v/all``, ``ssim_y/u/v/all`` (float64 [N]) from pp_metrics' sums
     (sse [N, 3] integers, ssim [N, 3]), plus ``mean``: the clip values (mean
@@ -48,7 +49,10 @@ def summarize(sse, ssim, fmt, w, h, matched=None, ms_terms=None, vif_terms=None,
     when asked for): adds ``vif_y`` [N] and ``vif_scales_y`` [N, 4] and their
     clip means (vif.summarize).  ``adm_terms`` (pp_adm's [N, 4, 6], spec
     PP-ADM-1; only when asked for): adds ``adm2_y`` [N] and ``adm_scales_y``
-    [N, 4] and their clip means (adm.summarize)."""
+    [N, 4] and their clip means (adm.summarize).  ``motion_terms`` (pp_motion's
+    [N] of the reference frames as shown, spec PP-MOTION-1; only when asked
+    for): adds ``motion_y`` and ``motion2_y`` [N] and their clip means
+    (motion.summarize)."""
     f = formats.fmt(fmt)
     sse = np.asarray(sse).reshape(-1, 3)
     ssim = np.asarray(ssim, dtype=np.float64).reshape(-1, 3)
@@ -98,6 +102,11 @@ def summarize(sse, ssim, fmt, w, h, matched=None, ms_terms=None, vif_terms=None,
         ad = adm.summarize(adm_terms, w, h, matched)
         mean.update(ad.pop("mean"))
         res.update(ad)
+    if motion_terms is not None:
+        from . import motion
+        mo = motion.summarize(motion_terms, w, h, matched)
+        mean.update(mo.pop("mean"))
+        res.update(mo)
     return res
 
 
@@ -113,7 +122,7 @@ def _map_entries(k0, n, in_rate, out_rate, n_in=None):
 
 
 def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, crop_from="yuv422p", ref_index=None,
-                     ms_ssim=False, vif=False, adm=False):
+                     ms_ssim=False, vif=False, adm=False, motion=False):
     """PP-METRIC-1 of the file ``dist_path`` (the PVS) against ``ref_path``
     (the SRC); returns ``summarize``'s dict.  Both are read with the chain's
     own readers (FFV1 AVIs through ffv1.open_avpvs_reader, anything else
@@ -146,7 +155,14 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, 
     pair (spec PP-VIF-1, ops.vif on the same resident frames).
 
     ``adm``: also the luma ADM (adm2) and its four per-scale values of every
-    frame pair (spec PP-ADM-1, ops.adm on the same resident frames)."""
+    frame pair (spec PP-ADM-1, ops.adm on the same resident frames).
+
+    ``motion``: also the motion and motion2 of the reference frames as shown
+    (spec PP-MOTION-1, ops.motion on the resident reference window with the
+    same frame map, after the scaler; the luma plane of the last frame shown
+    by a batch is kept as the next batch's ``prev``).  An unmatched frame of
+    an explicit map is read against the held reference frame: its difference
+    is 0 for its neighbours' sake and its own values are NaN."""
     import torch
 
     from . import ops
@@ -162,6 +178,7 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, 
         in_rate, out_rate = ref.rate, dist.rate
         win, win0, n_ref, ref_end = None, 0, 0, False  # resident reference frames [win0, n_ref), dist geometry
         outs, terms, vterms, aterms, k0 = [], [], [], [], 0
+        mterms, held = [], None  # PP-MOTION-1: the sums, and a copy of the luma plane of the last frame shown
         explicit = None if ref_index is None else np.asarray(ref_index, dtype=np.int64).reshape(-1)
         last = 0  # explicit map: the reference frame an unmatched distorted frame is read against (and not reported)
         for d in dists:
@@ -211,6 +228,10 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, 
                 vterms.append(ops.vif(win, d, ref_index=m - win0))
             if adm:
                 aterms.append(ops.adm(win, d, ref_index=m - win0))
+            if motion:
+                mterms.append(ops.motion(win, index=m - win0, prev=held).view(torch.int64))
+                # the window may be rebuilt before the next batch: a copy, not a view
+                held = win.view(0)[int(m[-1]) - win0:int(m[-1]) - win0 + 1].clone()
             k0 += d.n
         torch.cuda.current_stream(dev).synchronize()
     if outs:
@@ -227,10 +248,32 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, 
     at = None
     if adm:
         at = torch.cat(aterms).cpu().numpy() if aterms else np.zeros((0, 4, 6))
+    mt = None
+    if motion:
+        mt = torch.cat(mterms).cpu().numpy().view(np.uint64) if mterms else np.zeros((0,), np.uint64)
     if explicit is None:
-        return summarize(sse, ssim, dfmt, dw, dh, ms_terms=ms, vif_terms=vt, adm_terms=at)
+        return summarize(sse, ssim, dfmt, dw, dh, ms_terms=ms, vif_terms=vt, adm_terms=at, motion_terms=mt)
     return summarize(sse, ssim, dfmt, dw, dh, matched=explicit[:sse.shape[0]] >= 0, ms_terms=ms, vif_terms=vt,
-                     adm_terms=at)
+                     adm_terms=at, motion_terms=mt)
+
+
+VMAF_FEATURE_NAMES = ("adm2", "motion2", "vif_scale0", "vif_scale1", "vif_scale2", "vif_scale3")
+
+
+def vmaf_features(res, per_frame=False):
+    """The six elementary features the published VMAF models take, in
+    VMAF_FEATURE_NAMES' order, from a result with VIF, ADM and motion:
+    ``vmaf_features`` (the clip means), ``vmaf_feature_names`` and, with
+    per_frame, ``vmaf_features_frames`` [N][6]; NaN becomes null.  No model is
+    applied: the library ships none."""
+    mean = res["mean"]
+    out = {"vmaf_features": [json_value(v) for v in [mean["adm2_y"], mean["motion2_y"]] + list(mean["vif_scales_y"])],
+           "vmaf_feature_names": list(VMAF_FEATURE_NAMES)}
+    if per_frame:
+        out["vmaf_features_frames"] = [
+            [json_value(v) for v in [a, m] + list(row)]
+            for a, m, row in zip(res["adm2_y"], res["motion2_y"], res["vif_scales_y"])]
+    return out
 
 
 def report(res, ref_path, dist_path, per_frame=False):
@@ -243,7 +286,9 @@ def report(res, ref_path, dist_path, per_frame=False):
     frame, ``vif_y_frames`` and ``vif_scales_y_frames`` ([N][4]).  A result
     with ADM (summarize's adm_terms) adds ``adm2_y`` and ``adm_scales_y`` (four
     values) and, per frame, ``adm2_y_frames`` and ``adm_scales_y_frames``
-    ([N][4])."""
+    ([N][4]).  A result with motion (summarize's motion_terms) adds
+    ``motion_y`` and ``motion2_y`` and, per frame, ``motion_y_frames`` and
+    ``motion2_y_frames``."""
     out = {"ref": os.path.basename(ref_path), "file": os.path.basename(dist_path), "frames": int(res["frames"]),
            "spec": "PP-METRIC-1"}
     for k, v in res["mean"].items():
@@ -264,4 +309,7 @@ def report(res, ref_path, dist_path, per_frame=False):
         if "adm2_y" in res:
             out["adm2_y_frames"] = [json_value(v) for v in res["adm2_y"]]
             out["adm_scales_y_frames"] = [[json_value(v) for v in row] for row in res["adm_scales_y"]]
+        if "motion_y" in res:
+            out["motion_y_frames"] = [json_value(v) for v in res["motion_y"]]
+            out["motion2_y_frames"] = [json_value(v) for v in res["motion2_y"]]
     return out

@@ -527,6 +527,46 @@ def adm(ref_batch, dist_batch, ref_index=None, stream=None):
     return out
 
 
+def motion(batch_or_luma, bitdepth=None, index=None, prev=None, stream=None):
+    """Blurred-luma difference sums of a shown sequence (spec PP-MOTION-1,
+    pp_motion): a FrameBatch or its [N, H, W] luma tensor (any pitches;
+    ``bitdepth`` overrides what the input implies).  The sequence shown is
+    frame ``index[0]``, ``index[1]``, .. of the input (default: every frame in
+    order; repeats and backward steps allowed).  ``prev``: the frame shown
+    before the first, a FrameBatch or [1, H, W] / [H, W] luma of the same size
+    and depth.  Returns a device tensor uint64 [n] on the current stream:
+    sad[k] = sum |B(frame k) - B(frame k - 1)| over the plane, exact; sad[0]
+    without ``prev``, and every entry of a plane under 3 x 3, is 2^64 - 1 =
+    absent.  pixpath.motion.pool turns it into motion and motion2."""
+    s, sd = _luma(batch_or_luma)
+    d = sd if bitdepth is None else int(bitdepth)
+    nsrc, h, w = s.shape
+    idx = None
+    n = nsrc
+    if index is not None:
+        idx = np.ascontiguousarray(index, dtype=np.int32).reshape(-1)
+        n = int(idx.shape[0])
+    out = torch.empty((n,), dtype=torch.uint64, device=s.device)
+    if n == 0:  # an empty sequence has no data pointer to pass
+        return out
+    if nsrc == 0:
+        raise ValueError("index names frames of an empty batch")
+    es = s.element_size()
+    pp, pls = None, 0
+    if prev is not None:
+        p, pd = _luma(prev if hasattr(prev, "planes") or prev.dim() == 3 else prev[None])
+        if pd != sd or tuple(p.shape[1:]) != (h, w) or p.shape[0] < 1:
+            raise ValueError("prev must be one luma plane of the input's size and bit depth")
+        if p.device != s.device:
+            raise ValueError("prev is on another device")
+        pp, pls = ctypes.c_void_p(p.data_ptr()), p.stride(1) * es
+    ctx = context(s.device.index)
+    check(lib().pp_motion(ctx.handle, d, w, h, ctypes.c_void_p(s.data_ptr()), s.stride(1) * es, s.stride(0) * es, nsrc,
+                          None if idx is None else idx.ctypes.data, n, pp, pls, ctypes.c_void_p(out.data_ptr()),
+                          _stream(s, stream)))
+    return out
+
+
 def spinner_upload(rgba_frames, f, device=None):
     """Upload an RGBA8 animation [n, h, w, 4] (host) for stall compositing."""
     a = np.ascontiguousarray(rgba_frames, dtype=np.uint8)
