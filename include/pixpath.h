@@ -624,6 +624,54 @@ int pp_motion(pp_ctx *ctx, int bitdepth, int w, int h,
               const void *prev, int64_t prev_linesize,
               uint64_t *sad, void *stream);
 
+/* ---- Banding detection of a luma sequence (spec PP-BAND-1) ----
+ * A no-reference measure of banding (staircase gradients) modelled on CAMBI
+ * (Tandon et al., PCS 2021) as recalled and defined by DESIGN.md's text alone:
+ * no display-luminance model, a mask threshold, a tie rule of the mode filter
+ * and integer contrast values of its own.  Per shown frame: the luma is brought
+ * to the ten-bit scale (bitdepth 8: bytes, x << 2; 10: uint16 LE, min(x, 1023),
+ * PP-MOTION-1's rule), averaged over 2 x 2 against dither, masked to its flat
+ * areas (a 7 x 7 count of samples equal to their right and lower neighbour, at
+ * least 25), and reduced four times by a 3 x 3 mode filter and decimation by 2:
+ * scale s + 1 has (w_s + 1) / 2 x (h_s + 1) / 2 positions, and all five scales
+ * exist for every w, h >= 1.  At every masked position of every scale the
+ * masked samples of the values v - 4 .. v + 4 inside the window x window
+ * neighbourhood are counted (v the position's value; the same number of samples
+ * at every scale), and the contrast value is
+ *   Q = max over k = 1 .. 4 with v <= tvi[k-1] and both signs of
+ *       floor(1024 k n_0 n_k / ((n_0 + n_k) window^2))  <= 1023,
+ * 0 at an unmasked position.  The shown sequence is src[index[0]], ..,
+ * src[index[n-1]] (index: HOST array of n entries, NULL = identity, which
+ * needs n <= nsrc; an entry outside [0, nsrc) is PP_ERR_INVALID; repeats and
+ * backward steps are allowed and give identical rows).
+ *   window  odd, 3 .. 63; anything else is PP_ERR_INVALID
+ *   tvi     HOST array of four entries, the largest v at which a step of
+ *           k = 1 .. 4 codes counts; NULL = 1023 for all four.  The hook for a
+ *           display model; none ships.
+ *   hist    [n][5][1024] uint32, DEVICE, every element written and nothing
+ *           else: hist[k][s][q] = positions of scale s of frame k with Q = q;
+ *           the sum over q is w_s h_s.
+ * The banding index is host arithmetic on the histograms: pixpath/banding.py
+ * `pool`.  Everything is exact integer arithmetic (the quotient: two exact
+ * integers divided in fp64 and floored, which is the integer quotient here);
+ * the bins are added with integer atomics, so two runs give the same bits.
+ * Pitch padding never counts.  NULL ctx, src or hist, w or h < 1, n or nsrc
+ * < 0, a linesize below the row's bytes, 16-bit samples off the 2-byte grid
+ * and a bitdepth other than 8 or 10 are PP_ERR_INVALID; a plane past the 2 GiB
+ * buffer range is PP_ERR_UNSUPPORTED.  Arguments are checked before any HIP
+ * call; n == 0 is PP_OK and writes nothing.  Every sample is loaded as one
+ * element, whatever grid the pointer, linesize and frame stride lie on: the
+ * layout of the same samples cannot change a bit of the result.  The workspace
+ * (the five levels, 16 bits a position, of up to 256 frames or 1 GiB a launch:
+ * about 5.5 MB a frame at 1080p) belongs to the context.  Parity with libvmaf's
+ * CAMBI is unpinned: no libvmaf exists to compare with.  Added without raising
+ * PP_ABI_VERSION (still 7). */
+int pp_banding(pp_ctx *ctx, int bitdepth, int w, int h,
+               const void *src, int64_t src_linesize, int64_t src_frame_stride, int nsrc,
+               const int32_t *index, int n,
+               int window, const uint16_t *tvi,
+               uint32_t *hist, void *stream);
+
 /* ---- host helpers --------------------------------------------------------
  * vf_fps output->input frame map (lib/ffmpeg.py:832-834, :959-961, :1038,
  * :1179): map[k] = input frame shown at output frame k.  Returns the number of

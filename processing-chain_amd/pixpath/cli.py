@@ -19,7 +19,10 @@ the ffmpeg strings they replace).
           --vif adds the luma VIF and its four per-scale values (spec PP-VIF-1);
           --adm adds the luma ADM (adm2) and its four per-scale values (spec PP-ADM-1);
           --motion adds motion and motion2 of the reference frames as shown (spec PP-MOTION-1);
-          --vmaf-features implies the three and adds the six-value feature vector a VMAF model takes
+          --vmaf-features implies the three and adds the six-value feature vector a VMAF model takes;
+          --banding adds the banding index of the PVS, of its reference as shown and their difference (spec PP-BAND-1)
+  banding the banding index of one clip (spec PP-BAND-1): staircase gradients that PSNR and SSIM do not see;
+          --crop WxH [--avpvs-pix-fmt NAME] measures the picture inside a v210 / UYVY CPVS canvas
   framecrc FFmpeg's `-f framecrc` listing of a file: one GPU Adler-32 per frame (spec PP-HASH-1);
           --against FILE compares with a listing; `avpvs --framecrc FILE` lists what the writer was given
   stats  what is inside one clip (spec PP-STATS-1): per-plane range, mean, percentiles, used bits,
@@ -678,6 +681,8 @@ def cmd_metrics(args):
         kw["adm"] = True
     if args.motion:  # motion and motion2 of the reference frames as shown as well (spec PP-MOTION-1)
         kw["motion"] = True
+    if args.banding:  # the banding index of both clips and what the chain added (spec PP-BAND-1)
+        kw["banding"] = True
     if args.vmaf_features:  # the six elementary features of the published VMAF models; no model is applied
         kw.update(vif=True, adm=True, motion=True)
     res = metrics.metrics_of_files(args.ref, args.input, batch=args.batch, flags=args.flags, **kw)
@@ -753,6 +758,14 @@ def cmd_stats(args):
     res = stats.stats_of_file(args.input, batch=args.batch, pix_th=args.black_pix_th, pic_th=args.black_pic_th,
                               histogram=args.histogram, **kw)
     print(json.dumps(stats.report(res, args.input, per_frame=args.per_frame)))
+    return 0
+
+
+def cmd_banding(args):
+    """The banding index of a file (spec PP-BAND-1): one JSON line."""
+    from . import banding
+    res = banding.banding_of_file(args.input, batch=args.batch, window=args.window, **_crop_settings(args))
+    print(json.dumps(banding.report(res, args.input, per_frame=args.per_frame)))
     return 0
 
 
@@ -872,6 +885,9 @@ def main(argv=None):
                    help="add the luma ADM (adm2) and its four per-scale values (spec PP-ADM-1)")
     p.add_argument("--motion", action="store_true",
                    help="add motion and motion2 of the reference frames as shown (spec PP-MOTION-1)")
+    p.add_argument("--banding", action="store_true",
+                   help="add the banding index of the input, of the reference frames as shown and their difference "
+                        "(spec PP-BAND-1)")
     p.add_argument("--vmaf-features", action="store_true",
                    help="implies --vif --adm --motion; add the feature vector adm2, motion2, vif_scale0..3 "
                         "(vmaf_features, vmaf_feature_names; with --per-frame vmaf_features_frames)")
@@ -916,6 +932,18 @@ def main(argv=None):
                    help="a frame is black from this share of black luma samples (blackdetect's pic_th)")
     p.add_argument("--batch", type=int, default=32)
     p.set_defaults(fn=cmd_stats)
+
+    p = sub.add_parser("banding")
+    p.add_argument("input", metavar="INPUT")
+    p.add_argument("--per-frame", action="store_true")
+    p.add_argument("--window", type=int, default=None, metavar="N",
+                   help="window of the contrast value, odd, 3 .. 63 (default: by the picture's size, 33 at 1080p)")
+    p.add_argument("--crop", default=None, metavar="WxH",
+                   help="the input is a v210 / UYVY CPVS: measure the WxH AVPVS picture inside its canvas")
+    p.add_argument("--avpvs-pix-fmt", default=None, metavar="NAME",
+                   help="pixel format of the AVPVS the CPVS was padded from (yuv420p...: rows offset rounded to even)")
+    p.add_argument("--batch", type=int, default=32)
+    p.set_defaults(fn=cmd_banding)
 
     args = ap.parse_args(argv)
     # GPU FFV1 applies to AVI files (the reference's AVPVS container); Y4M /

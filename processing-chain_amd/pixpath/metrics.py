@@ -33,7 +33,7 @@ def _psnr(mse, peak):
 
 
 def summarize(sse, ssim, fmt, w, h, matched=None, ms_terms=None, vif_terms=None, adm_terms=None,
-              motion_terms=None):
+              motion_terms=None, banding_terms=None):
     """Host side of PP-METRIC-1: per-frame arrays ``mse_y/u/v/all``,
     ``psnr_y/u/v/all``, ``ssim_y/u/v/all`` (float64 [N]) from pp_metrics' sums
     (sse [N, 3] integers, ssim [N, 3]), plus ``mean``: the clip values (mean
@@ -52,7 +52,10 @@ def summarize(sse, ssim, fmt, w, h, matched=None, ms_terms=None, vif_terms=None,
     [N, 4] and their clip means (adm.summarize).  ``motion_terms`` (pp_motion's
     [N] of the reference frames as shown, spec PP-MOTION-1; only when asked
     for): adds ``motion_y`` and ``motion2_y`` [N] and their clip means
-    (motion.summarize)."""
+    (motion.summarize).  ``banding_terms`` (pp_banding's [N, 5, 1024] of the
+    distorted frames and of the reference frames as shown, spec PP-BAND-1; only
+    when asked for): adds ``banding_y``, ``banding_ref_y`` and their difference
+    ``banding_added_y`` [N] and their clip means (banding.pool)."""
     f = formats.fmt(fmt)
     sse = np.asarray(sse).reshape(-1, 3)
     ssim = np.asarray(ssim, dtype=np.float64).reshape(-1, 3)
@@ -107,6 +110,15 @@ def summarize(sse, ssim, fmt, w, h, matched=None, ms_terms=None, vif_terms=None,
         mo = motion.summarize(motion_terms, w, h, matched)
         mean.update(mo.pop("mean"))
         res.update(mo)
+    if banding_terms is not None:
+        from . import banding
+        bd, br = (banding.pool(t)[0] for t in banding_terms)
+        for key, v in (("banding_y", bd), ("banding_ref_y", br), ("banding_added_y", bd - br)):
+            if matched is not None:
+                v[~matched] = np.nan
+            res[key] = v
+            ok = v[~np.isnan(v)]
+            mean[key] = float(ok.mean()) if ok.size else float("nan")
     return res
 
 
@@ -122,7 +134,7 @@ def _map_entries(k0, n, in_rate, out_rate, n_in=None):
 
 
 def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, crop_from="yuv422p", ref_index=None,
-                     ms_ssim=False, vif=False, adm=False, motion=False):
+                     ms_ssim=False, vif=False, adm=False, motion=False, banding=False):
     """PP-METRIC-1 of the file ``dist_path`` (the PVS) against ``ref_path``
     (the SRC); returns ``summarize``'s dict.  Both are read with the chain's
     own readers (FFV1 AVIs through ffv1.open_avpvs_reader, anything else
@@ -162,7 +174,13 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, 
     same frame map, after the scaler; the luma plane of the last frame shown
     by a batch is kept as the next batch's ``prev``).  An unmatched frame of
     an explicit map is read against the held reference frame: its difference
-    is 0 for its neighbours' sake and its own values are NaN."""
+    is 0 for its neighbours' sake and its own values are NaN.
+
+    ``banding``: also the banding index of every distorted frame, of the
+    reference frame shown with it (spec PP-BAND-1, ops.banding on the resident
+    frames with the same frame map, after the scaler; the window is
+    banding.default_window of the distorted picture) and their difference,
+    what the chain added."""
     import torch
 
     from . import ops
@@ -178,6 +196,7 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, 
         in_rate, out_rate = ref.rate, dist.rate
         win, win0, n_ref, ref_end = None, 0, 0, False  # resident reference frames [win0, n_ref), dist geometry
         outs, terms, vterms, aterms, k0 = [], [], [], [], 0
+        bterms, brterms = [], []  # PP-BAND-1: histograms of the distorted frames and of the reference frames as shown
         mterms, held = [], None  # PP-MOTION-1: the sums, and a copy of the luma plane of the last frame shown
         explicit = None if ref_index is None else np.asarray(ref_index, dtype=np.int64).reshape(-1)
         last = 0  # explicit map: the reference frame an unmatched distorted frame is read against (and not reported)
@@ -232,6 +251,9 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, 
                 mterms.append(ops.motion(win, index=m - win0, prev=held).view(torch.int64))
                 # the window may be rebuilt before the next batch: a copy, not a view
                 held = win.view(0)[int(m[-1]) - win0:int(m[-1]) - win0 + 1].clone()
+            if banding:
+                bterms.append(ops.banding(d))
+                brterms.append(ops.banding(win, index=m - win0))
             k0 += d.n
         torch.cuda.current_stream(dev).synchronize()
     if outs:
@@ -251,10 +273,15 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, 
     mt = None
     if motion:
         mt = torch.cat(mterms).cpu().numpy().view(np.uint64) if mterms else np.zeros((0,), np.uint64)
+    bt = None
+    if banding:
+        from .banding import BINS, SCALES
+        bt = tuple(torch.cat(t).cpu().numpy() if t else np.zeros((0, SCALES, BINS), np.uint32) for t in (bterms, brterms))
     if explicit is None:
-        return summarize(sse, ssim, dfmt, dw, dh, ms_terms=ms, vif_terms=vt, adm_terms=at, motion_terms=mt)
+        return summarize(sse, ssim, dfmt, dw, dh, ms_terms=ms, vif_terms=vt, adm_terms=at, motion_terms=mt,
+                         banding_terms=bt)
     return summarize(sse, ssim, dfmt, dw, dh, matched=explicit[:sse.shape[0]] >= 0, ms_terms=ms, vif_terms=vt,
-                     adm_terms=at, motion_terms=mt)
+                     adm_terms=at, motion_terms=mt, banding_terms=bt)
 
 
 VMAF_FEATURE_NAMES = ("adm2", "motion2", "vif_scale0", "vif_scale1", "vif_scale2", "vif_scale3")
@@ -288,7 +315,9 @@ def report(res, ref_path, dist_path, per_frame=False):
     values) and, per frame, ``adm2_y_frames`` and ``adm_scales_y_frames``
     ([N][4]).  A result with motion (summarize's motion_terms) adds
     ``motion_y`` and ``motion2_y`` and, per frame, ``motion_y_frames`` and
-    ``motion2_y_frames``."""
+    ``motion2_y_frames``.  A result with banding (summarize's banding_terms)
+    adds ``banding_y``, ``banding_ref_y`` and ``banding_added_y`` and, per
+    frame, the three lists with ``_frames``."""
     out = {"ref": os.path.basename(ref_path), "file": os.path.basename(dist_path), "frames": int(res["frames"]),
            "spec": "PP-METRIC-1"}
     for k, v in res["mean"].items():
@@ -312,4 +341,7 @@ def report(res, ref_path, dist_path, per_frame=False):
         if "motion_y" in res:
             out["motion_y_frames"] = [json_value(v) for v in res["motion_y"]]
             out["motion2_y_frames"] = [json_value(v) for v in res["motion2_y"]]
+        if "banding_y" in res:
+            for key in ("banding_y", "banding_ref_y", "banding_added_y"):
+                out[key + "_frames"] = [json_value(v) for v in res[key]]
     return out

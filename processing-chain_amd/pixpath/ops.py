@@ -567,6 +567,46 @@ def motion(batch_or_luma, bitdepth=None, index=None, prev=None, stream=None):
     return out
 
 
+def banding(batch_or_luma, bitdepth=None, index=None, window=None, tvi=None, stream=None):
+    """Contrast-value histograms of a shown sequence (spec PP-BAND-1,
+    pp_banding): a FrameBatch or its [N, H, W] luma tensor (any pitches;
+    ``bitdepth`` overrides what the input implies).  The sequence shown is
+    frame ``index[0]``, ``index[1]``, .. of the input (default: every frame in
+    order; repeats and backward steps allowed).  ``window``: the odd window
+    size 3 .. 63 (default pixpath.banding.default_window(w, h)).  ``tvi``: four
+    values, the largest y at which a step of k = 1 .. 4 codes counts (default:
+    1023 for all four, no display model).  Returns a device tensor uint32
+    [n, 5, 1024] on the current stream: hist[k, s, q] = positions of scale s of
+    frame k with contrast value q.  pixpath.banding.pool turns it into the
+    banding index."""
+    from . import banding as _banding
+    s, sd = _luma(batch_or_luma)
+    d = sd if bitdepth is None else int(bitdepth)
+    nsrc, h, w = s.shape
+    idx = None
+    n = nsrc
+    if index is not None:
+        idx = np.ascontiguousarray(index, dtype=np.int32).reshape(-1)
+        n = int(idx.shape[0])
+    out = torch.empty((n, _banding.SCALES, _banding.BINS), dtype=torch.uint32, device=s.device)
+    if n == 0:  # an empty sequence has no data pointer to pass
+        return out
+    if nsrc == 0:
+        raise ValueError("index names frames of an empty batch")
+    win = _banding.default_window(w, h) if window is None else int(window)
+    tv = None
+    if tvi is not None:
+        tv = np.ascontiguousarray(tvi, dtype=np.uint16).reshape(-1)
+        if tv.shape != (4,):
+            raise ValueError("tvi needs four entries")
+    es = s.element_size()
+    ctx = context(s.device.index)
+    check(lib().pp_banding(ctx.handle, d, w, h, ctypes.c_void_p(s.data_ptr()), s.stride(1) * es, s.stride(0) * es, nsrc,
+                           None if idx is None else idx.ctypes.data, n, win, None if tv is None else tv.ctypes.data,
+                           ctypes.c_void_p(out.data_ptr()), _stream(s, stream)))
+    return out
+
+
 def spinner_upload(rgba_frames, f, device=None):
     """Upload an RGBA8 animation [n, h, w, 4] (host) for stall compositing."""
     a = np.ascontiguousarray(rgba_frames, dtype=np.uint8)

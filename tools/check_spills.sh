@@ -27,14 +27,14 @@ for f in ["/tmp/strip_u16.s", "/tmp/strip_u16_chain.s", "/tmp/strip_u8.s", "/tmp
 print("instances with VGPR spills:", bad)
 PY
 # every kernel of every HIP source: no private (scratch) segment
-for f in scale cpvs pack unpack siti metrics framecrc stats align msssim vif adm motion; do
+for f in scale cpvs pack unpack siti metrics framecrc stats align msssim vif adm motion banding; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -x hip csrc/$f.hip --cuda-device-only -S -o /tmp/$f.s 2>/dev/null &
 done
 wait
 python3 - <<'PY'
 import re
 bad = []
-for f in ["scale", "cpvs", "pack", "unpack", "siti", "metrics", "framecrc", "stats", "align", "msssim", "vif", "adm", "motion", "strip_u16", "strip_u16_chain", "strip_u8", "strip_u8_chain", "strip_u16_fused", "strip_u8_fused"]:
+for f in ["scale", "cpvs", "pack", "unpack", "siti", "metrics", "framecrc", "stats", "align", "msssim", "vif", "adm", "motion", "banding", "strip_u16", "strip_u16_chain", "strip_u8", "strip_u8_chain", "strip_u16_fused", "strip_u8_fused"]:
     txt = open('/tmp/%s.s' % f).read()
     for b in txt.split('  - .agpr_count:')[1:]:
         name = re.search(r"\.name:\s+(\S+)", b).group(1)
