@@ -9,7 +9,7 @@
 // and everything after that is fp64.  Level s of the Daubechies-2 transform has
 // (w_{s-1} + 1) / 2 x (h_{s-1} + 1) / 2 coefficients; coefficient i of an axis
 // reads inputs 2i - 1 .. 2i + 2, mirrored without repeating the edge sample
-// (vif.hip's rule) by index arithmetic at load time.  Rows are filtered first
+// (mirror_index) by index arithmetic at load time.  Rows are filtered first
 // (along the row), then columns.
 //
 // One fused kernel per scale (adm_scale<T, S>): a workgroup (256 lanes, 4
@@ -30,14 +30,12 @@
 // Every load is one element at a mirrored, clamped position, whatever the
 // pointer and the pitches are: there is one path, and the layout of the same
 // samples cannot change a bit of the result.
-// Reduction: lane -> wave (xor butterfly) -> workgroup (4 values through LDS in
-// wave order) -> one partial per unit; adm_finalize adds a (frame, scale)'s
+// Reduction: block_gather / block_total -> one partial per unit; adm_finalize adds a (frame, scale)'s
 // partials in unit order, or writes NaN.  No atomics: two runs give the same
 // bits.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <type_traits>
 
 #include "analysis_dev.hpp"
 #include "analysis_host.hpp"
@@ -50,8 +48,6 @@ constexpr int kAdmWaves = 4;                  // waves per workgroup
 constexpr int kAdmLanes = 64 * kAdmWaves;
 constexpr int kAdmTileCols = kAdmLanes - 2;   // coefficient columns of a tile: a lane each, less the halo
 constexpr int kAdmBandRows = 32;              // coefficient rows of a tile
-constexpr int kAdmIdx = 256;                  // ref_index entries per launch (kernel arguments)
-constexpr int64_t kAdmWork = 1 << 30;         // bytes of A bands a launch may hold (at least one frame's)
 
 struct AdmPartial {
     double v[kAdmSums];  // sums over the unit's positions of the region
@@ -75,18 +71,13 @@ struct AdmArgs {
     double lo[4], hi[4];            // the analysis pair
     double rf[kAdmScales][3];       // 1 / Q(s, theta), theta = H, V, D
     double cos2;                    // cos^2 of one degree
-    int32_t idx[kAdmIdx];           // reference frame of distorted frame k
+    int32_t idx[kFrameMap];         // reference frame of distorted frame k
 };
 
 // One plane of the level a scale reads: the samples themselves (T) for scale
 // 0, the A band of the level before (doubles) after that.
-struct AdmPlane {
-    const uint8_t *base;
-    int64_t ls;
-};
-
 template <typename T, int S>
-__device__ __forceinline__ AdmPlane adm_plane(const AdmArgs &a, int k, int side) {
+__device__ __forceinline__ LevelPlane adm_plane(const AdmArgs &a, int k, int side) {
     if constexpr (S > 0) {
         const double *q = a.pyr + (int64_t)(2 * k + side) * a.plane + a.off[S - 1];
         return {reinterpret_cast<const uint8_t *>(q), (int64_t)a.w[S] * 8};
@@ -94,22 +85,6 @@ __device__ __forceinline__ AdmPlane adm_plane(const AdmArgs &a, int k, int side)
         if (side) return {a.dist + (int64_t)k * a.dfs, a.dls};
         return {a.ref + (int64_t)a.idx[k] * a.rfs, a.rls};
     }
-}
-
-template <typename T>
-__device__ __forceinline__ double adm_sample(const AdmPlane &p, int y, int x, double mul) {
-    const T v = reinterpret_cast<const T *>(p.base + (int64_t)y * p.ls)[x];
-    if constexpr (std::is_same<T, double>::value) return v;
-    else return (double)v * mul;  // exact: mul is a power of two
-}
-
-// Index i of a row of n samples under the mirrored border (-1 -> 1, n -> n - 2,
-// n + 1 -> n - 3); an index further out (it only reaches coefficients that do
-// not exist) is clamped, so every load goes to an element of the plane.
-__device__ __forceinline__ int adm_mirror(int i, int n) {
-    i = i < 0 ? -i : i;
-    i = i >= n ? 2 * (n - 1) - i : i;
-    return min(max(i, 0), n - 1);
 }
 
 __device__ __forceinline__ double adm_dot4(const double f[4], double v0, double v1, double v2, double v3) {
@@ -143,10 +118,10 @@ __device__ __forceinline__ double adm_decouple(const double o[3], const double t
 template <typename T, int S>
 __global__ __launch_bounds__(kAdmLanes) void adm_scale(const AdmArgs a) {
     __shared__ double s_m[2][kAdmLanes];
-    __shared__ AdmPartial s_red[kAdmWaves];
+    __shared__ double s_red[kAdmWaves][kAdmSums];
     const int wi = a.w[S], hi = a.h[S], wo = a.w[S + 1], ho = a.h[S + 1];
     const int tx = a.tx[S], ups = a.unit0[S + 1] - a.unit0[S];
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int k = blockIdx.x / ups, t = blockIdx.x - k * ups;
     const int band = t / tx, tile = t - band * tx;
     const int x0 = tile * kAdmTileCols, y0 = band * kAdmBandRows;
@@ -156,10 +131,10 @@ __global__ __launch_bounds__(kAdmLanes) void adm_scale(const AdmArgs a) {
     const bool reg_c = own && c >= a.mw[S] && c < wo - a.mw[S];
     const bool busy = x0 - 1 + wave * 64 < wo;     // some lane of the wave has a column that exists (uniform)
     const bool store = S + 1 < a.nsc;              // a later scale reads A (uniform)
-    const AdmPlane pl[2] = {adm_plane<T, S>(a, k, 0), adm_plane<T, S>(a, k, 1)};
+    const LevelPlane pl[2] = {adm_plane<T, S>(a, k, 0), adm_plane<T, S>(a, k, 1)};
     int cx[4];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) cx[q] = adm_mirror(2 * c - 1 + q, wi);
+    for (int q = 0; q < 4; ++q) cx[q] = mirror_index(2 * c - 1 + q, wi);
     double *dst[2];
 #pragma unroll
     for (int p = 0; p < 2; ++p)
@@ -169,11 +144,11 @@ __global__ __launch_bounds__(kAdmLanes) void adm_scale(const AdmArgs a) {
     auto fetch = [&](int y) {  // input rows y, y + 1
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            const int yy = adm_mirror(y + i, hi);
+            const int yy = mirror_index(y + i, hi);
 #pragma unroll
             for (int p = 0; p < 2; ++p)
 #pragma unroll
-                for (int q = 0; q < 4; ++q) nx[i][p][q] = adm_sample<T>(pl[p], yy, cx[q], a.mul);
+                for (int q = 0; q < 4; ++q) nx[i][p][q] = level_sample<T>(pl[p], yy, cx[q], a.mul);
         }
     };
     double ring[4][4];  // input rows 2r - 1 .. 2r + 2 filtered along the row: {ref lo, ref hi, dist lo, dist hi}
@@ -236,15 +211,10 @@ __global__ __launch_bounds__(kAdmLanes) void adm_scale(const AdmArgs a) {
 #pragma unroll
         for (int i = 0; i < 3; ++i) { pp1[i] = p[i]; pq1[i] = q[i]; }
     }
-#pragma unroll
-    for (int i = 0; i < kAdmSums; ++i) {
-        const double v = wave_sum(acc[i]);
-        if (lane == 0) s_red[wave].v[i] = v;
-    }
-    __syncthreads();
-    if (tid < kAdmSums) {
+    block_gather(acc, s_red);
+    if (tid < kAdmSums) {  // a lane per sum
         AdmPartial *out = a.part + (int64_t)k * a.unit0[kAdmScales] + a.unit0[S] + t;
-        out->v[tid] = ((s_red[0].v[tid] + s_red[1].v[tid]) + s_red[2].v[tid]) + s_red[3].v[tid];
+        out->v[tid] = block_total(s_red, tid);
     }
 }
 
@@ -273,29 +243,15 @@ extern "C" int pp_adm(pp_ctx *ctx, int bitdepth, int w, int h, const void *ref, 
                       int64_t ref_frame_stride, int nref, const void *dist, int64_t dist_linesize,
                       int64_t dist_frame_stride, int ndist, const int32_t *ref_index, double *out, void *stream) {
     if (!ctx || !ref || !dist || !out) PP_FAIL(PP_ERR_INVALID, "null argument");
-    if (bitdepth != 8 && bitdepth != 10) PP_FAIL(PP_ERR_INVALID, "bitdepth %d (8 or 10)", bitdepth);
-    if (w < 1 || h < 1) PP_FAIL(PP_ERR_INVALID, "frame %dx%d", w, h);
+    LumaPlanes lp;
+    if (int e = luma_open(lp, bitdepth, w, h)) return e;
     if (ndist < 0) PP_FAIL(PP_ERR_INVALID, "ndist %d < 0", ndist);
     if (nref < 0) PP_FAIL(PP_ERR_INVALID, "nref %d < 0", nref);
-    const int es = bitdepth > 8 ? 2 : 1;
-    PlaneGeom g{};
-    g.pw = w; g.ph = h; g.rb = (int64_t)w * es;
-    bool aligned = true;  // unused: one element-wise path
-    pp_frames fr{}, fd{};
-    fr.data[0] = const_cast<void *>(ref); fr.linesize[0] = ref_linesize; fr.frame_stride[0] = ref_frame_stride;
-    fd.data[0] = const_cast<void *>(dist); fd.linesize[0] = dist_linesize; fd.frame_stride[0] = dist_frame_stride;
-    if (int e = check_plane(&fr, 0, g, aligned, 0, "ref ")) return e;
-    if (int e = check_plane(&fd, 0, g, aligned, 0, "dist ")) return e;
-    if (((uintptr_t)dist | (uint64_t)dist_linesize | (uint64_t)dist_frame_stride | (uintptr_t)ref |
-         (uint64_t)ref_linesize | (uint64_t)ref_frame_stride) & (es - 1))
-        PP_FAIL(PP_ERR_INVALID, "16-bit samples off the 2-byte grid");
-    if (ref_index) {
-        for (int k = 0; k < ndist; ++k)
-            if (ref_index[k] < 0 || ref_index[k] >= nref)
-                PP_FAIL(PP_ERR_INVALID, "ref_index[%d] = %d outside the %d reference frames", k, ref_index[k], nref);
-    } else if (ndist > nref) {
-        PP_FAIL(PP_ERR_INVALID, "ndist %d > nref %d without ref_index", ndist, nref);
-    }
+    if (int e = luma_plane(lp, ref, ref_linesize, ref_frame_stride, "ref ")) return e;
+    if (int e = luma_plane(lp, dist, dist_linesize, dist_frame_stride, "dist ")) return e;
+    if (int e = luma_close(lp)) return e;  // one element-wise path: lp.aligned is not looked at
+    if (int e = check_frame_map(ref_index, ndist, nref, kRefIndexMap)) return e;
+    const int es = lp.es;
     if (ndist == 0) return PP_OK;
 
     AdmArgs a{};
@@ -338,18 +294,15 @@ extern "C" int pp_adm(pp_ctx *ctx, int bitdepth, int w, int h, const void *ref, 
     hipStream_t st = static_cast<hipStream_t>(stream);
     PP_HIP(hipSetDevice(ctx->device));
     const int upf = a.unit0[kAdmScales];
-    // frames per launch: the map's room in the kernel arguments, and a workspace of about kAdmWork
     const int64_t pyr_bytes = (int64_t)sizeof(double) * 2 * a.plane;
-    const int per = (int)std::min<int64_t>(std::min(ndist, kAdmIdx), std::max<int64_t>(1, kAdmWork / std::max<int64_t>(pyr_bytes, 1)));
+    const int per = frames_per_launch(ndist, pyr_bytes);
     const size_t part_bytes = sizeof(AdmPartial) * (size_t)per * std::max(upf, 1);
     if (int e = grow(ctx->adm, part_bytes + (size_t)per * (size_t)pyr_bytes)) return e;
     a.part = static_cast<AdmPartial *>(ctx->adm.buf);
     a.pyr = reinterpret_cast<double *>(static_cast<uint8_t *>(ctx->adm.buf) + part_bytes);
 
-    // a workgroup per tile: far below 2^31 for planes inside the 2 GiB range and kAdmIdx frames
+    // a workgroup per tile: far below 2^31 for planes inside the 2 GiB range and kFrameMap frames
     auto grid = [](int64_t n) { return dim3((unsigned)n); };
-    // the frame map travels in the kernel arguments, kAdmIdx frames per launch (as
-    // pp_vif's); launches on one stream run in order, so they share the workspace
     for (int k0 = 0; k0 < ndist; k0 += per) {
         AdmArgs b = a;
         b.nk = std::min(per, ndist - k0);

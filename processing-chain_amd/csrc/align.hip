@@ -63,7 +63,6 @@ constexpr int kAlnTileRows = kAlnWaves * kAlnLaneRows;
 constexpr int kAlnTileBytes = kAlnLanes * kAlnLaneBytes;
 constexpr int kAlnGroup = 4;       // reference pieces (loads) in flight per lane
 constexpr int kAlnChunk = 32;      // candidates between two exchanges through LDS
-constexpr int kAlnIdx = 256;       // `first` entries per launch (kernel arguments)
 
 struct AlnArgs {
     const uint8_t *dist, *ref;
@@ -74,7 +73,7 @@ struct AlnArgs {
     int nref, ncand;
     uint64_t *part;  // [nk][tiles][ncand]
     uint64_t *sse;   // [nk][ncand]
-    int32_t first[kAlnIdx];
+    int32_t first[kFrameMap];
 };
 
 typedef uint16_t aln_v2u16 __attribute__((ext_vector_type(2)));
@@ -219,24 +218,17 @@ extern "C" int pp_frame_sse_band(pp_ctx *ctx, int bitdepth, int w, int h, const 
                                  int64_t ref_frame_stride, int nref, const int32_t *first, int ncand, uint64_t *sse,
                                  void *stream) {
     if (!ctx || !dist || !ref || !first || !sse) PP_FAIL(PP_ERR_INVALID, "null argument");
-    if (bitdepth != 8 && bitdepth != 10) PP_FAIL(PP_ERR_INVALID, "bitdepth %d (8 or 10)", bitdepth);
-    if (w < 1 || h < 1) PP_FAIL(PP_ERR_INVALID, "frame %dx%d", w, h);
+    LumaPlanes lp;
+    if (int e = luma_open(lp, bitdepth, w, h)) return e;
     if (ndist < 0) PP_FAIL(PP_ERR_INVALID, "ndist %d < 0", ndist);
     if (nref < 0) PP_FAIL(PP_ERR_INVALID, "nref %d < 0", nref);
     if (ncand < 1) PP_FAIL(PP_ERR_INVALID, "ncand %d < 1", ncand);
-    const int es = bitdepth > 8 ? 2 : 1;
-    PlaneGeom g{};
-    g.pw = w; g.ph = h; g.rb = (int64_t)w * es;
-    bool dal = true, ral = true;
-    pp_frames fd{}, fr{};
-    fd.data[0] = const_cast<void *>(dist); fd.linesize[0] = dist_linesize; fd.frame_stride[0] = dist_frame_stride;
-    fr.data[0] = const_cast<void *>(ref); fr.linesize[0] = ref_linesize; fr.frame_stride[0] = ref_frame_stride;
     // a tile's rows below the plane stay inside the buffer range too
-    if (int e = check_plane(&fd, 0, g, dal, kAlnTileRows, "dist ")) return e;
-    if (int e = check_plane(&fr, 0, g, ral, kAlnTileRows, "ref ")) return e;
-    if (((uintptr_t)dist | (uint64_t)dist_linesize | (uint64_t)dist_frame_stride | (uintptr_t)ref |
-         (uint64_t)ref_linesize | (uint64_t)ref_frame_stride) & (es - 1))
-        PP_FAIL(PP_ERR_INVALID, "16-bit samples off the 2-byte grid");
+    if (int e = luma_plane(lp, dist, dist_linesize, dist_frame_stride, "dist ", kAlnTileRows)) return e;
+    if (int e = luma_plane(lp, ref, ref_linesize, ref_frame_stride, "ref ", kAlnTileRows)) return e;
+    if (int e = luma_close(lp)) return e;
+    const int es = lp.es;
+    const PlaneGeom &g = lp.g;
     if (ndist == 0) return PP_OK;
 
     AlnArgs a{};
@@ -252,20 +244,18 @@ extern "C" int pp_frame_sse_band(pp_ctx *ctx, int bitdepth, int w, int h, const 
 
     hipStream_t st = static_cast<hipStream_t>(stream);
     PP_HIP(hipSetDevice(ctx->device));
-    const int per = std::min(ndist, kAlnIdx);
+    const int per = frames_per_launch(ndist);
     if (int e = grow(ctx->aln, sizeof(uint64_t) * (size_t)per * a.tiles * ncand)) return e;
     a.part = static_cast<uint64_t *>(ctx->aln.buf);
 
     using KFn = void (*)(const AlnArgs);
-    const bool aligned = dal && ral;  // one source off the 16-B grid: both go element by element
+    const bool aligned = lp.aligned;  // one source off the 16-B grid: both go element by element
 #define PP_ALN_K(ES)                                                                        \
     (!aligned ? align_kernel<ES, false, true> : ragged ? align_kernel<ES, true, true> \
                                                        : align_kernel<ES, true, false>)
     const KFn kern = es == 2 ? PP_ALN_K(2) : PP_ALN_K(1);
 #undef PP_ALN_K
-    // `first` travels in the kernel arguments, kAlnIdx frames per launch (as
-    // pp_metrics' ref_index); launches on one stream run in order, so they
-    // share the workspace
+    // `first` travels in the kernel arguments as a frame map does
     for (int k0 = 0; k0 < ndist; k0 += per) {
         AlnArgs b = a;
         b.nk = std::min(per, ndist - k0);

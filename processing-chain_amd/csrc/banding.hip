@@ -10,7 +10,7 @@
 // v + d is the code v + d itself, and neither an unmasked sample nor the
 // code kBdOutside the contrast kernel puts around the plane ever equals one.
 //
-// Three kernels per launch of up to kBdIdx frames:
+// Three kernels per launch of up to kFrameMap frames:
 //   banding_prep      steps 1 - 3: a workgroup takes a tile of 32 rows x 64
 //                     columns, computes y0 of the tile and a margin of 3 (4 to
 //                     the right and below) into LDS from clamped element loads,
@@ -65,7 +65,6 @@ constexpr int kBdMaxWin = 63;
 constexpr int kBdSpan = kBdTile + kBdMaxWin - 1;   // the largest tile with its margin
 constexpr int kBdCopies = 4;                       // LDS copies of a bin
 constexpr int kBdChunk = 4;                        // tiles a workgroup walks before it adds its bins
-constexpr int kBdIdx = 256;                        // index entries per launch (kernel arguments)
 constexpr uint32_t kBdUnmasked = 0x8000u;          // bit of a code: m_s = 0
 constexpr uint32_t kBdOutside = 0x8000u;           // code of a window sample outside the plane
 constexpr uint32_t kBdNone = 0xffffu;              // a lane's position outside the plane
@@ -81,7 +80,7 @@ struct BdArgs {
     int nk, window;
     int tvi[4];
     uint32_t *hist;                 // [nk][5][1024]
-    int32_t idx[kBdIdx];            // source frame of shown frame k
+    int32_t idx[kFrameMap];         // source frame of shown frame k
 };
 
 template <typename T>
@@ -278,28 +277,16 @@ extern "C" int pp_banding(pp_ctx *ctx, int bitdepth, int w, int h, const void *s
                           int64_t src_frame_stride, int nsrc, const int32_t *index, int n, int window,
                           const uint16_t *tvi, uint32_t *hist, void *stream) {
     if (!ctx || !src || !hist) PP_FAIL(PP_ERR_INVALID, "null argument");
-    if (bitdepth != 8 && bitdepth != 10) PP_FAIL(PP_ERR_INVALID, "bitdepth %d (8 or 10)", bitdepth);
-    if (w < 1 || h < 1) PP_FAIL(PP_ERR_INVALID, "frame %dx%d", w, h);
+    LumaPlanes lp;
+    if (int e = luma_open(lp, bitdepth, w, h)) return e;
     if (n < 0) PP_FAIL(PP_ERR_INVALID, "n %d < 0", n);
     if (nsrc < 0) PP_FAIL(PP_ERR_INVALID, "nsrc %d < 0", nsrc);
     if (window < 3 || window > kBdMaxWin || !(window & 1))
         PP_FAIL(PP_ERR_INVALID, "window %d (odd, 3 .. %d)", window, kBdMaxWin);
-    const int es = bitdepth > 8 ? 2 : 1;
-    PlaneGeom g{};
-    g.pw = w; g.ph = h; g.rb = (int64_t)w * es;
-    bool aligned = true;
-    pp_frames fr{};
-    fr.data[0] = const_cast<void *>(src); fr.linesize[0] = src_linesize; fr.frame_stride[0] = src_frame_stride;
-    if (int e = check_plane(&fr, 0, g, aligned, 0, "src ")) return e;
-    if (((uintptr_t)src | (uint64_t)src_linesize | (uint64_t)src_frame_stride) & (es - 1))
-        PP_FAIL(PP_ERR_INVALID, "16-bit samples off the 2-byte grid");
-    if (index) {
-        for (int k = 0; k < n; ++k)
-            if (index[k] < 0 || index[k] >= nsrc)
-                PP_FAIL(PP_ERR_INVALID, "index[%d] = %d outside the %d source frames", k, index[k], nsrc);
-    } else if (n > nsrc) {
-        PP_FAIL(PP_ERR_INVALID, "n %d > nsrc %d without index", n, nsrc);
-    }
+    if (int e = luma_plane(lp, src, src_linesize, src_frame_stride, "src ")) return e;
+    if (int e = luma_close(lp)) return e;
+    if (int e = check_frame_map(index, n, nsrc, kIndexMap)) return e;
+    const int es = lp.es;
     if (n == 0) return PP_OK;
 
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -320,9 +307,7 @@ extern "C" int pp_banding(pp_ctx *ctx, int bitdepth, int w, int h, const void *s
         a.unit0[s + 1] = a.unit0[s] + (int)((tiles + kBdChunk - 1) / kBdChunk);
     }
     a.frame = codes;
-    // the levels of up to kBdIdx frames or 1 GiB a launch (one frame at least)
-    const int64_t fit = std::max<int64_t>(1, ((int64_t)1 << 30) / (codes * 2));
-    const int per = (int)std::min<int64_t>(std::min(n, kBdIdx), fit);
+    const int per = frames_per_launch(n, codes * 2);
     if (int e = grow(ctx->bnd, (size_t)per * (size_t)codes * 2)) return e;
     a.ws = static_cast<uint16_t *>(ctx->bnd.buf);
     const unsigned ptiles = (unsigned)(((w + kBdMaskCols - 1) / kBdMaskCols) * (int64_t)((h + kBdMaskRows - 1) / kBdMaskRows));
@@ -338,7 +323,7 @@ extern "C" int pp_banding(pp_ctx *ctx, int bitdepth, int w, int h, const void *s
         for (int s = 0; s + 1 < kBdScales; ++s)
             hipLaunchKernelGGL(banding_down, dim3((unsigned)(((int64_t)a.w[s + 1] * a.h[s + 1] + 255) / 256), b.nk),
                                dim3(256), 0, st, b, s);
-        // far below 2^31 workgroups for planes inside the 2 GiB range and kBdIdx frames
+        // far below 2^31 workgroups for planes inside the 2 GiB range and kFrameMap frames
         hipLaunchKernelGGL(banding_contrast, dim3((unsigned)((int64_t)b.nk * a.unit0[kBdScales])), dim3(256), 0, st, b);
     }
     PP_HIP(hipGetLastError());

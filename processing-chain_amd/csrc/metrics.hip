@@ -46,7 +46,6 @@ constexpr int kMetLaneBytes = 16;   // one load per lane and row
 constexpr int kMetOwnLanes = 63;    // lanes of a wave that own blocks; lane 63 is the halo lane
 constexpr int kMetWaves = 4;        // waves per workgroup
 constexpr int kBandBlocks = 16;     // block rows per band (64 sample rows), plus one halo block row
-constexpr int kMetIdx = 256;        // ref_index entries per launch (kernel arguments)
 
 struct MetPartial {
     uint64_t sse;
@@ -63,7 +62,7 @@ struct MetArgs {
     int identity;              // ref frame = dist frame (idx unused)
     int depth;
     MetPartial *part;          // [nk][tiles]
-    int32_t idx[kMetIdx];
+    int32_t idx[kFrameMap];
 };
 
 template <typename T>
@@ -298,8 +297,8 @@ extern "C" int pp_metrics(pp_ctx *ctx, int fmt, int w, int h, const pp_frames *r
                              : (!aligned ? metrics_kernel<uint8_t, false, true>
                                          : ragged ? metrics_kernel<uint8_t, true, true> : metrics_kernel<uint8_t, true, false>);
     // identity: one launch over all frames; a map travels in the kernel
-    // arguments, kMetIdx dist frames per launch (as pp_stall_compose's)
-    const int per = ref_index ? kMetIdx : nframes;
+    // arguments, kFrameMap dist frames per launch (as pp_stall_compose's)
+    const int per = ref_index ? kFrameMap : nframes;
     for (int k0 = 0; k0 < nframes; k0 += per) {
         MetArgs b = a;
         b.nk = std::min(per, nframes - k0);

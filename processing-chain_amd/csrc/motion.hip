@@ -42,8 +42,8 @@
 // Pitch padding of a ragged last piece is loaded as it is and filtered, but
 // reaches no output: the slots of columns w and w + 1 are overwritten by the
 // mirror and everything right of them is cleared from B.
-// Reduction: lane -> wave (xor butterfly) -> workgroup (4 values through LDS)
-// -> one 64-bit partial per (frame, tile); motion_finalize adds a frame's
+// Reduction: block_sum (four waves < 2^30 each: 32 bits) -> one 64-bit partial
+// per (frame, tile); motion_finalize adds a frame's
 // partials in tile order.  No atomics: two runs give the same bits.
 #include <algorithm>
 #include <cstring>
@@ -58,7 +58,6 @@ constexpr int kMoLaneRows = 16;                     // rows of a tile one wave o
 constexpr int kMoTileRows = kMoWaves * kMoLaneRows; // rows of a tile
 constexpr int kMoPieces = 62;                       // output pieces of a tile's row (64 lanes less the halo)
 constexpr int kMoSeg = 4;                           // shown frames a workgroup walks
-constexpr int kMoIdx = 256;                         // index entries per launch (kernel arguments)
 constexpr uint32_t kMoF0 = 3571, kMoF1 = 16004, kMoF2 = 26386;
 
 struct MoArgs {
@@ -70,16 +69,8 @@ struct MoArgs {
     int first_absent;           // frame 0 of the launch has no previous frame
     uint64_t *part;             // [nk][tiles]
     uint64_t *sad;              // [nk]
-    int32_t idx[kMoIdx];        // source frame of shown frame k
+    int32_t idx[kFrameMap];     // source frame of shown frame k
 };
-
-// Index i of an axis of n samples under the mirrored border (PP-VIF-1's rule),
-// clamped so that every load goes to an element of the plane.
-__device__ __forceinline__ int mo_mirror(int i, int n) {
-    i = i < 0 ? -i : i;
-    i = i >= n ? 2 * (n - 1) - i : i;
-    return min(max(i, 0), n - 1);
-}
 
 // One workgroup per (segment, tile) of the launch, segment-major.
 template <typename T, bool ALIGNED>
@@ -88,7 +79,7 @@ __global__ __launch_bounds__(256) void motion_kernel(const MoArgs a) {
     constexpr int D = ES == 2 ? 10 : 8;
     constexpr int ROWD = 64 * NP + 2;  // dwords of an LDS row: a pair of slots either side of the wave's samples
     __shared__ __align__(16) uint32_t s_t[kMoWaves][ROWD];
-    __shared__ uint32_t s_red[kMoWaves];
+    __shared__ uint32_t s_red[kMoWaves][1];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int seg = blockIdx.x / a.tiles, tile = blockIdx.x - seg * a.tiles;
@@ -134,7 +125,7 @@ __global__ __launch_bounds__(256) void motion_kernel(const MoArgs a) {
         r0f = __builtin_amdgcn_readfirstlane(r0f);
         uint32_t ring[5][4];
         uint32_t nxt[4];
-        load_piece<T, ALIGNED>(nxt, rs, base, ls, mo_mirror(r0f - 2, h), h, cl, rb, in);
+        load_piece<T, ALIGNED>(nxt, rs, base, ls, mirror_index(r0f - 2, h), h, cl, rb, in);
         uint32_t sad = 0;
 #pragma unroll
         for (int i = 0; i < kMoLaneRows + 4; ++i) {  // input row r0 - 2 + i of the band, ring slot i % 5
@@ -148,7 +139,7 @@ __global__ __launch_bounds__(256) void motion_kernel(const MoArgs a) {
                 ring[i % 5][d] = q;
             }
             if (i + 1 < kMoLaneRows + 4)  // travels while this row is filtered
-                load_piece<T, ALIGNED>(nxt, rs, base, ls, mo_mirror(r0f - 2 + i + 1, h), h, cl, rb, in);
+                load_piece<T, ALIGNED>(nxt, rs, base, ls, mirror_index(r0f - 2 + i + 1, h), h, cl, rb, in);
             if (i < 4) continue;
             const int u = i - 4;  // output row r0 + u: taps are ring slots (i - 4 .. i) % 5
             // V
@@ -194,11 +185,12 @@ __global__ __launch_bounds__(256) void motion_kernel(const MoArgs a) {
             }
         }
         if (seed) continue;  // uniform
-        sad = wave_sum(sad);
-        if (lane == 0) s_red[wave] = sad;
-        __syncthreads();  // the next write of s_red lies behind the next frame's row barriers
-        if (threadIdx.x == 0)
-            a.part[(int64_t)k * a.tiles + tile] = (uint64_t)s_red[0] + s_red[1] + s_red[2] + s_red[3];
+        // 32 bits hold the four waves: 64 rows x 62 x 16 columns x 65472 = 4.16e9 < 2^32 = 4.29e9
+        // (kMoTileRows x kMoPieces x 16 / es samples of at most 65472; 8 bits is the larger case)
+        static_assert((uint64_t)kMoTileRows * kMoPieces * 16 * 65472 < (uint64_t)1 << 32, "a tile's sum needs 64 bits");
+        uint32_t tot[1] = {sad};
+        block_sum(tot, s_red);  // the next write of s_red lies behind the next frame's row barriers
+        if (threadIdx.x == 0) a.part[(int64_t)k * a.tiles + tile] = tot[0];
     }
 }
 
@@ -224,32 +216,17 @@ extern "C" int pp_motion(pp_ctx *ctx, int bitdepth, int w, int h, const void *sr
                          int64_t src_frame_stride, int nsrc, const int32_t *index, int n, const void *prev,
                          int64_t prev_linesize, uint64_t *sad, void *stream) {
     if (!ctx || !src || !sad) PP_FAIL(PP_ERR_INVALID, "null argument");
-    if (bitdepth != 8 && bitdepth != 10) PP_FAIL(PP_ERR_INVALID, "bitdepth %d (8 or 10)", bitdepth);
-    if (w < 1 || h < 1) PP_FAIL(PP_ERR_INVALID, "frame %dx%d", w, h);
+    LumaPlanes lp;
+    if (int e = luma_open(lp, bitdepth, w, h)) return e;
     if (n < 0) PP_FAIL(PP_ERR_INVALID, "n %d < 0", n);
     if (nsrc < 0) PP_FAIL(PP_ERR_INVALID, "nsrc %d < 0", nsrc);
-    const int es = bitdepth > 8 ? 2 : 1;
-    PlaneGeom g{};
-    g.pw = w; g.ph = h; g.rb = (int64_t)w * es;
-    PlaneGeom gp = g;
-    bool aligned = true;
-    pp_frames fs{}, fp{};
-    fs.data[0] = const_cast<void *>(src); fs.linesize[0] = src_linesize; fs.frame_stride[0] = src_frame_stride;
-    if (int e = check_plane(&fs, 0, g, aligned, 0, "src ")) return e;
-    if (prev) {
-        fp.data[0] = const_cast<void *>(prev); fp.linesize[0] = prev_linesize;
-        if (int e = check_plane(&fp, 0, gp, aligned, 0, "prev ", true)) return e;
-    }
-    if (((uintptr_t)src | (uint64_t)src_linesize | (uint64_t)src_frame_stride | (uintptr_t)prev |
-         (prev ? (uint64_t)prev_linesize : 0)) & (es - 1))
-        PP_FAIL(PP_ERR_INVALID, "16-bit samples off the 2-byte grid");
-    if (index) {
-        for (int k = 0; k < n; ++k)
-            if (index[k] < 0 || index[k] >= nsrc)
-                PP_FAIL(PP_ERR_INVALID, "index[%d] = %d outside the %d source frames", k, index[k], nsrc);
-    } else if (n > nsrc) {
-        PP_FAIL(PP_ERR_INVALID, "n %d > nsrc %d without index", n, nsrc);
-    }
+    if (int e = luma_plane(lp, src, src_linesize, src_frame_stride, "src ")) return e;
+    if (prev)
+        if (int e = luma_plane(lp, prev, prev_linesize, 0, "prev ", 0, true)) return e;
+    if (int e = luma_close(lp)) return e;
+    if (int e = check_frame_map(index, n, nsrc, kIndexMap)) return e;
+    const int es = lp.es;
+    const bool aligned = lp.aligned;
     if (n == 0) return PP_OK;
 
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -258,11 +235,11 @@ extern "C" int pp_motion(pp_ctx *ctx, int bitdepth, int w, int h, const void *sr
     MoArgs a{};
     a.src = static_cast<const uint8_t *>(src);
     a.ls = src_linesize; a.fs = src_frame_stride;
-    a.w = w; a.h = h; a.rb = (int)g.rb;
+    a.w = w; a.h = h; a.rb = (int)lp.g.rb;
     const int cols = kMoPieces * 16 / es;  // output columns of a tile
     a.tx = (w + cols - 1) / cols;
     a.tiles = a.tx * ((h + kMoTileRows - 1) / kMoTileRows);
-    const int per = std::min(n, kMoIdx);
+    const int per = frames_per_launch(n);
     if (!none) {
         if (int e = grow(ctx->mot, sizeof(uint64_t) * (size_t)per * a.tiles)) return e;
         a.part = static_cast<uint64_t *>(ctx->mot.buf);
@@ -270,8 +247,6 @@ extern "C" int pp_motion(pp_ctx *ctx, int bitdepth, int w, int h, const void *sr
     using KFn = void (*)(const MoArgs);
     const KFn kern = es == 2 ? (aligned ? motion_kernel<uint16_t, true> : motion_kernel<uint16_t, false>)
                              : (aligned ? motion_kernel<uint8_t, true> : motion_kernel<uint8_t, false>);
-    // the frame map travels in the kernel arguments, kMoIdx frames per launch (as
-    // pp_vif's); launches on one stream run in order, so they share the workspace
     for (int k0 = 0; k0 < n; k0 += per) {
         MoArgs b = a;
         b.nk = std::min(per, n - k0);
@@ -290,7 +265,7 @@ extern "C" int pp_motion(pp_ctx *ctx, int bitdepth, int w, int h, const void *sr
         b.sad = sad + k0;
         if (!none) {
             const int segs = (b.nk + kMoSeg - 1) / kMoSeg;
-            // a workgroup per (segment, tile): far below 2^31 for planes inside the 2 GiB range and kMoIdx frames
+            // a workgroup per (segment, tile): far below 2^31 for planes inside the 2 GiB range and kFrameMap frames
             hipLaunchKernelGGL(kern, dim3((unsigned)((int64_t)segs * a.tiles)), dim3(256), 0, st, b);
         }
         hipLaunchKernelGGL(motion_finalize, dim3((b.nk + 63) / 64), dim3(64), 0, st, b.part, b.nk, a.tiles,

@@ -23,23 +23,16 @@
 //
 // Statistics (vif_stat<T, N>, N = 17, 9, 5, 3): a workgroup (256 lanes, 4
 // waves) owns one unit = (frame k, tile of kVifTileCols positions x
-// kVifBandRows rows) of one scale; a lane owns one column.  Per input row of
-// the band (kVifBandRows + N - 1 of them, mirrored):
-//   - every lane loads one sample of each plane (lanes 0 .. N - 2 one more: the
-//     halo right of the tile), the next row's while this one is worked on, and
-//     puts both as doubles into one of two LDS rows (one barrier a row);
-//   - H: the lane reads its N neighbours (x, y) from LDS and filters the five
-//     quantities x, y, x^2, y^2, x y into slot row % N of a ring of N rows x 5
-//     doubles held in registers (the row loop is unrolled by N, so every slot
-//     is a fixed register; 170 VGPRs at N = 17);
-//   - V: from row N - 1 on, the ring's N rows give the position's five means,
-//     then the spec's arithmetic (two IEEE divisions, two log2) gives num and
-//     den, added to the lane's two sums.
+// kVifBandRows rows) of one scale; a lane owns one column.  The band's
+// kVifBandRows + N - 1 input rows (mirrored) go through window_moments
+// (analysis_dev.hpp; its ring takes 170 VGPRs at N = 17): every lane loads one
+// sample of each plane a row (lanes 0 .. N - 2 one more: the halo right of the
+// tile), and a position's five means go through the spec's arithmetic (two
+// IEEE divisions, two log2) into num and den, added to the lane's two sums.
 // Every load is one element at a mirrored, clamped position, whatever the
 // pointer and the pitches are: there is one path, and the layout of the same
 // samples cannot change a bit of the result.
-// Reduction: lane -> wave (xor butterfly) -> workgroup (4 values through LDS in
-// wave order) -> one partial per unit; vif_finalize adds a (frame, scale)'s
+// Reduction: block_sum -> one partial per unit; vif_finalize adds a (frame, scale)'s
 // partials in unit order, or writes NaN.  No atomics: two runs give the same
 // bits.
 #include <algorithm>
@@ -58,16 +51,11 @@ constexpr int kVifWaves = 4;             // waves per workgroup
 constexpr int kVifTileCols = 64 * kVifWaves;  // columns of a tile: one per lane
 constexpr int kVifBandRows = 64;         // rows of a statistics tile
 constexpr int kVifDecRows = 32;          // output rows of a decimation tile
-constexpr int kVifIdx = 256;             // ref_index entries per launch (kernel arguments)
-constexpr int64_t kVifWork = 1 << 30;    // bytes of pyramids a launch may hold (at least one frame's)
 constexpr double kVifEps = 1e-10;
 constexpr double kVifNoise = 2.0;        // sigma_n^2
 
 constexpr int vif_taps(int s) { return s == 0 ? 17 : s == 1 ? 9 : s == 2 ? 5 : 3; }
 constexpr int vif_scale_of(int n) { return n == 17 ? 0 : n == 9 ? 1 : n == 5 ? 2 : 3; }
-// The window is symmetric (g[q] and g[n - 1 - q] are the same bits): the kernels
-// read its first half only, which halves the scalar registers it takes.
-__host__ __device__ constexpr int vif_tap(int q, int n) { return q < n - 1 - q ? q : n - 1 - q; }
 
 struct VifPartial {
     double num, den;  // sums over the unit's positions
@@ -88,18 +76,13 @@ struct VifArgs {
     VifPartial *part;              // [nk][units]
     double *out;                   // [nk][4][2]
     double g[kVifScales][kVifMaxTaps];
-    int32_t idx[kVifIdx];          // reference frame of distorted frame k
+    int32_t idx[kFrameMap];        // reference frame of distorted frame k
 };
 
 // One plane of one scale: scale 0 the samples themselves (T), the others the
 // pyramid's doubles.
-struct VifPlane {
-    const uint8_t *base;
-    int64_t ls;
-};
-
 template <typename T>
-__device__ __forceinline__ VifPlane vif_plane(const VifArgs &a, int k, int side, int s) {
+__device__ __forceinline__ LevelPlane vif_plane(const VifArgs &a, int k, int side, int s) {
     if constexpr (std::is_same<T, double>::value) {
         const double *q = a.pyr + (int64_t)(2 * k + side) * a.plane + a.off[s];
         return {reinterpret_cast<const uint8_t *>(q), (int64_t)a.ws[s] * 8};
@@ -107,22 +90,6 @@ __device__ __forceinline__ VifPlane vif_plane(const VifArgs &a, int k, int side,
         if (side) return {a.dist + (int64_t)k * a.dfs, a.dls};
         return {a.ref + (int64_t)a.idx[k] * a.rfs, a.rls};
     }
-}
-
-template <typename T>
-__device__ __forceinline__ double vif_sample(const VifPlane &p, int y, int x, double mul) {
-    const T v = reinterpret_cast<const T *>(p.base + (int64_t)y * p.ls)[x];
-    if constexpr (std::is_same<T, double>::value) return v;
-    else return (double)v * mul;  // exact: mul is a power of two
-}
-
-// Index i of a row of n samples under the mirrored border; an index more than
-// one reflection away (it only reaches positions that do not exist) is clamped,
-// so every load goes to an element of the plane.
-__device__ __forceinline__ int vif_mirror(int i, int n) {
-    i = i < 0 ? -i : i;
-    i = i >= n ? 2 * (n - 1) - i : i;
-    return min(max(i, 0), n - 1);
 }
 
 // Level s + 1 of both pyramids from level s (T = the sample type for s = 0,
@@ -142,21 +109,21 @@ __global__ __launch_bounds__(256) void vif_decimate(const VifArgs a) {
         const int pl = blockIdx.x / per;  // 2 k + (0: ref, 1: dist)
         const int t = blockIdx.x - pl * per;
         const int band = t / tx, tile = t - band * tx;
-        const VifPlane p = vif_plane<T>(a, pl >> 1, pl & 1, s);
+        const LevelPlane p = vif_plane<T>(a, pl >> 1, pl & 1, s);
         const int xo0 = tile * kVifTileCols, yo0 = band * kVifDecRows;
         const int nout = min(kVifDecRows, ho - yo0);
         const int nin = 2 * (nout - 1) + N;  // input rows of the band
         const bool own = xo0 + tid < wo;
         const bool busy = xo0 + wave * 64 < wo;  // some lane of the wave owns a column (uniform)
         // LDS entry j of a row is input column 2 xo0 - R + j
-        const int c0 = vif_mirror(2 * xo0 - R + 2 * tid, wi), c1 = vif_mirror(2 * xo0 - R + 2 * tid + 1, wi);
-        const int ch = vif_mirror(2 * xo0 - R + 2 * kVifTileCols + tid, wi);
+        const int c0 = mirror_index(2 * xo0 - R + 2 * tid, wi), c1 = mirror_index(2 * xo0 - R + 2 * tid + 1, wi);
+        const int ch = mirror_index(2 * xo0 - R + 2 * kVifTileCols + tid, wi);
         double n0, n1, nh = 0.0;  // the next row's samples
         auto fetch = [&](int i) {
-            const int y = vif_mirror(2 * yo0 - R + i, hi);
-            n0 = vif_sample<T>(p, y, c0, a.mul);
-            n1 = vif_sample<T>(p, y, c1, a.mul);
-            if (halo) nh = vif_sample<T>(p, y, ch, a.mul);
+            const int y = mirror_index(2 * yo0 - R + i, hi);
+            n0 = level_sample<T>(p, y, c0, a.mul);
+            n1 = level_sample<T>(p, y, c1, a.mul);
+            if (halo) nh = level_sample<T>(p, y, ch, a.mul);
         };
         double *dst = a.pyr + (int64_t)pl * a.plane + a.off[s + 1] + (int64_t)yo0 * wo + min(xo0 + tid, wo - 1);
         double ring[N];
@@ -177,7 +144,7 @@ __global__ __launch_bounds__(256) void vif_decimate(const VifArgs a) {
 #pragma unroll
                 for (int q = 0; q < N; ++q) {
                     const double v = row[2 * tid + q];
-                    hsum = q ? __builtin_fma(g[vif_tap(q, N)], v, hsum) : g[0] * v;
+                    hsum = q ? __builtin_fma(g[sym_tap(q, N)], v, hsum) : g[0] * v;
                 }
                 ring[j] = hsum;
                 if (i < N - 1 || ((i - (N - 1)) & 1)) continue;  // uniform: V at the even rows only
@@ -185,7 +152,7 @@ __global__ __launch_bounds__(256) void vif_decimate(const VifArgs a) {
 #pragma unroll
                 for (int q = 0; q < N; ++q) {  // tap q is input row i - (N - 1) + q
                     const double x = ring[(j + 1 + q) % N];
-                    v = q ? __builtin_fma(g[vif_tap(q, N)], x, v) : g[0] * x;
+                    v = q ? __builtin_fma(g[sym_tap(q, N)], x, v) : g[0] * x;
                 }
                 if (own) dst[(int64_t)((i - (N - 1)) >> 1) * wo] = v;
             }
@@ -218,81 +185,35 @@ template <typename T, int N>
 __global__ __launch_bounds__(256) void vif_stat(const VifArgs a) {
     constexpr int R = N / 2, s = vif_scale_of(N);
     __shared__ __align__(16) double2 s_row[2][kVifTileCols + N - 1];
-    __shared__ VifPartial s_red[kVifWaves];
+    __shared__ double s_red[kVifWaves][2];
     const int ws = a.ws[s], hs = a.hs[s], tx = a.tx[s];
     const int ups = a.unit0[s + 1] - a.unit0[s];
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const double *g = a.g[s];
-    const bool halo = tid < N - 1;
-    {
-        const int k = blockIdx.x / ups, t = blockIdx.x - k * ups;
-        const int band = t / tx, tile = t - band * tx;
-        const int x0 = tile * kVifTileCols, y0 = band * kVifBandRows;
-        const int nin = min(kVifBandRows, hs - y0) + N - 1;  // input rows of the band
-        const bool own = x0 + tid < ws;            // the lane's column is a position
-        const bool busy = x0 + wave * 64 < ws;     // some lane of the wave has one (uniform)
-        const VifPlane pa = vif_plane<T>(a, k, 0, s), pb = vif_plane<T>(a, k, 1, s);
-        // LDS entry j of a row is column x0 - R + j
-        const int cx = vif_mirror(x0 - R + tid, ws), hx = vif_mirror(x0 - R + kVifTileCols + tid, ws);
-        double na, nb, nha = 0.0, nhb = 0.0;  // the next row's samples
-        auto fetch = [&](int i) {
-            const int y = vif_mirror(y0 - R + i, hs);
-            na = vif_sample<T>(pa, y, cx, a.mul);
-            nb = vif_sample<T>(pb, y, cx, a.mul);
-            if (halo) {
-                nha = vif_sample<T>(pa, y, hx, a.mul);
-                nhb = vif_sample<T>(pb, y, hx, a.mul);
-            }
-        };
-        double ring[N][5];
-        double anum = 0.0, aden = 0.0;
-        fetch(0);
-        for (int i0 = 0; i0 < nin; i0 += N) {
-#pragma unroll
-            for (int j = 0; j < N; ++j) {
-                const int i = i0 + j;  // input row of the band; its ring slot is j
-                if (i >= nin) break;   // uniform
-                double2 *row = s_row[i & 1];
-                row[tid] = make_double2(na, nb);
-                if (halo) row[kVifTileCols + tid] = make_double2(nha, nhb);
-                // this row has landed; the row before it has been read by every wave, so the
-                // next one may overwrite it
-                __syncthreads();
-                if (i + 1 < nin) fetch(i + 1);  // travels while this row is filtered
-                if (!busy) continue;
-                double h[5];
-#pragma unroll
-                for (int q = 0; q < N; ++q) {
-                    const double2 v = row[tid + q];
-                    const double m[5] = {v.x, v.y, v.x * v.x, v.y * v.y, v.x * v.y};
-#pragma unroll
-                    for (int c = 0; c < 5; ++c) h[c] = q ? __builtin_fma(g[vif_tap(q, N)], m[c], h[c]) : g[0] * m[c];
-                }
-#pragma unroll
-                for (int c = 0; c < 5; ++c) ring[j][c] = h[c];
-                if (i < N - 1) continue;  // uniform
-                double v[5];
-#pragma unroll
-                for (int q = 0; q < N; ++q)  // tap q is input row i - (N - 1) + q
-#pragma unroll
-                    for (int c = 0; c < 5; ++c) {
-                        const double x = ring[(j + 1 + q) % N][c];
-                        v[c] = q ? __builtin_fma(g[vif_tap(q, N)], x, v[c]) : g[0] * x;
-                    }
-                double num, den;
-                vif_position(v, num, den);
-                if (own) { anum += num; aden += den; }
-            }
-        }
-        anum = wave_sum(anum);
-        aden = wave_sum(aden);
-        if (lane == 0) { s_red[wave].num = anum; s_red[wave].den = aden; }
-        __syncthreads();
-        if (tid == 0) {
-            VifPartial *out = a.part + (int64_t)k * a.unit0[kVifScales] + a.unit0[s] + t;
-            out->num = ((s_red[0].num + s_red[1].num) + s_red[2].num) + s_red[3].num;
-            out->den = ((s_red[0].den + s_red[1].den) + s_red[2].den) + s_red[3].den;
-        }
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int k = blockIdx.x / ups, t = blockIdx.x - k * ups;
+    const int band = t / tx, tile = t - band * tx;
+    const int x0 = tile * kVifTileCols, y0 = band * kVifBandRows;
+    const int nin = min(kVifBandRows, hs - y0) + N - 1;  // input rows of the band
+    const bool own = x0 + tid < ws;            // the lane's column is a position
+    const bool busy = x0 + wave * 64 < ws;     // some lane of the wave has one (uniform)
+    const LevelPlane pa = vif_plane<T>(a, k, 0, s), pb = vif_plane<T>(a, k, 1, s);
+    // LDS entry j of a row is column x0 - R + j
+    const int cx = mirror_index(x0 - R + tid, ws), hx = mirror_index(x0 - R + kVifTileCols + tid, ws);
+    auto fetch = [&](int i, bool halo, double2 &nx, double2 &nh) {
+        const int y = mirror_index(y0 - R + i, hs);
+        nx = make_double2(level_sample<T>(pa, y, cx, a.mul), level_sample<T>(pb, y, cx, a.mul));
+        if (halo) nh = make_double2(level_sample<T>(pa, y, hx, a.mul), level_sample<T>(pb, y, hx, a.mul));
+    };
+    double acc[2] = {0.0, 0.0};  // num, den
+    window_moments<N, kVifTileCols, double2>(s_row, a.g[s], nin, busy, fetch, [&](const double v[5]) {
+        double num, den;
+        vif_position(v, num, den);
+        if (own) { acc[0] += num; acc[1] += den; }
+    });
+    block_sum(acc, s_red);
+    if (tid == 0) {
+        VifPartial *out = a.part + (int64_t)k * a.unit0[kVifScales] + a.unit0[s] + t;
+        out->num = acc[0];
+        out->den = acc[1];
     }
 }
 
@@ -320,29 +241,15 @@ extern "C" int pp_vif(pp_ctx *ctx, int bitdepth, int w, int h, const void *ref, 
                       int64_t ref_frame_stride, int nref, const void *dist, int64_t dist_linesize,
                       int64_t dist_frame_stride, int ndist, const int32_t *ref_index, double *out, void *stream) {
     if (!ctx || !ref || !dist || !out) PP_FAIL(PP_ERR_INVALID, "null argument");
-    if (bitdepth != 8 && bitdepth != 10) PP_FAIL(PP_ERR_INVALID, "bitdepth %d (8 or 10)", bitdepth);
-    if (w < 1 || h < 1) PP_FAIL(PP_ERR_INVALID, "frame %dx%d", w, h);
+    LumaPlanes lp;
+    if (int e = luma_open(lp, bitdepth, w, h)) return e;
     if (ndist < 0) PP_FAIL(PP_ERR_INVALID, "ndist %d < 0", ndist);
     if (nref < 0) PP_FAIL(PP_ERR_INVALID, "nref %d < 0", nref);
-    const int es = bitdepth > 8 ? 2 : 1;
-    PlaneGeom g{};
-    g.pw = w; g.ph = h; g.rb = (int64_t)w * es;
-    bool aligned = true;  // unused: one element-wise path
-    pp_frames fr{}, fd{};
-    fr.data[0] = const_cast<void *>(ref); fr.linesize[0] = ref_linesize; fr.frame_stride[0] = ref_frame_stride;
-    fd.data[0] = const_cast<void *>(dist); fd.linesize[0] = dist_linesize; fd.frame_stride[0] = dist_frame_stride;
-    if (int e = check_plane(&fr, 0, g, aligned, 0, "ref ")) return e;
-    if (int e = check_plane(&fd, 0, g, aligned, 0, "dist ")) return e;
-    if (((uintptr_t)dist | (uint64_t)dist_linesize | (uint64_t)dist_frame_stride | (uintptr_t)ref |
-         (uint64_t)ref_linesize | (uint64_t)ref_frame_stride) & (es - 1))
-        PP_FAIL(PP_ERR_INVALID, "16-bit samples off the 2-byte grid");
-    if (ref_index) {
-        for (int k = 0; k < ndist; ++k)
-            if (ref_index[k] < 0 || ref_index[k] >= nref)
-                PP_FAIL(PP_ERR_INVALID, "ref_index[%d] = %d outside the %d reference frames", k, ref_index[k], nref);
-    } else if (ndist > nref) {
-        PP_FAIL(PP_ERR_INVALID, "ndist %d > nref %d without ref_index", ndist, nref);
-    }
+    if (int e = luma_plane(lp, ref, ref_linesize, ref_frame_stride, "ref ")) return e;
+    if (int e = luma_plane(lp, dist, dist_linesize, dist_frame_stride, "dist ")) return e;
+    if (int e = luma_close(lp)) return e;  // one element-wise path: lp.aligned is not looked at
+    if (int e = check_frame_map(ref_index, ndist, nref, kRefIndexMap)) return e;
+    const int es = lp.es;
     if (ndist == 0) return PP_OK;
 
     VifArgs a{};
@@ -373,19 +280,16 @@ extern "C" int pp_vif(pp_ctx *ctx, int bitdepth, int w, int h, const void *ref, 
 
     hipStream_t st = static_cast<hipStream_t>(stream);
     PP_HIP(hipSetDevice(ctx->device));
-    // frames per launch: the map's room in the kernel arguments, and a workspace of about kVifWork
     const int64_t pyr_bytes = (int64_t)sizeof(double) * 2 * a.plane;
-    const int per = (int)std::min<int64_t>(std::min(ndist, kVifIdx), std::max<int64_t>(1, kVifWork / std::max<int64_t>(pyr_bytes, 1)));
+    const int per = frames_per_launch(ndist, pyr_bytes);
     const int upf = a.unit0[kVifScales];
     const size_t part_bytes = sizeof(VifPartial) * (size_t)per * std::max(upf, 1);
     if (int e = grow(ctx->vif, part_bytes + (size_t)per * (size_t)pyr_bytes)) return e;
     a.part = static_cast<VifPartial *>(ctx->vif.buf);
     a.pyr = reinterpret_cast<double *>(static_cast<uint8_t *>(ctx->vif.buf) + part_bytes);
 
-    // a workgroup per tile: far below 2^31 for planes inside the 2 GiB range and kVifIdx frames
+    // a workgroup per tile: far below 2^31 for planes inside the 2 GiB range and kFrameMap frames
     auto grid = [](int64_t n) { return dim3((unsigned)n); };
-    // the frame map travels in the kernel arguments, kVifIdx frames per launch (as
-    // pp_ms_ssim's); launches on one stream run in order, so they share the workspace
     for (int k0 = 0; k0 < ndist; k0 += per) {
         VifArgs b = a;
         b.nk = std::min(per, ndist - k0);

@@ -12,6 +12,8 @@ import math
 
 import numpy as np
 
+from .clips import nan_mean
+
 SCALES = 4
 SUMS = 6               # per scale: x^3 of H, V, D, then |rf o|^3 of H, V, D
 MIN_SIZE = 33          # the smallest width and height with all four scales
@@ -21,7 +23,7 @@ AMPLITUDES = ((0.67234, 0.72709), (0.41317, 0.49428), (0.22727, 0.28688), (0.117
 TILE_COLS = 254        # kAdmTileCols: coefficient columns of a workgroup's tile (256 lanes less the halo)
 WAVE_COLS = 64         # of one wave; the first wave's first lane is the halo
 BAND_ROWS = 32         # kAdmBandRows: coefficient rows of a tile
-FRAMES_PER_LAUNCH = 256  # kAdmIdx
+FRAMES_PER_LAUNCH = 256  # kFrameMap (csrc/analysis_host.hpp)
 
 
 def filters():
@@ -97,10 +99,6 @@ def summarize(terms, w, h, matched=None):
         t[~np.asarray(matched, dtype=bool)] = np.nan
     scales, adm2 = pool(t, w, h)
     res = {"adm2_y": adm2.reshape(-1), "adm_scales_y": scales.reshape(-1, SCALES)}
-
-    def mean(v):
-        v = v[~np.isnan(v)]
-        return float(v.mean()) if v.size else float("nan")
-    res["mean"] = {"adm2_y": mean(res["adm2_y"]),
-                   "adm_scales_y": [mean(res["adm_scales_y"][:, s]) for s in range(SCALES)]}
+    res["mean"] = {"adm2_y": nan_mean(res["adm2_y"]),
+                   "adm_scales_y": [nan_mean(res["adm_scales_y"][:, s]) for s in range(SCALES)]}
     return res

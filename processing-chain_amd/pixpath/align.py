@@ -24,7 +24,7 @@ WAVE_ROWS = 16     # kAlnLaneRows: rows of a tile one wave holds
 TILE_ROWS = 64     # kAlnTileRows: rows of a unit (4 waves)
 GROUP = 4          # kAlnGroup: reference pieces in flight per lane
 CHUNK = 32         # kAlnChunk: candidates between two exchanges through LDS
-FIRST_PER_LAUNCH = 256  # kAlnIdx: `first` entries per launch
+FIRST_PER_LAUNCH = 256  # kFrameMap: `first` entries per launch
 
 ABSENT = np.uint64(0xFFFFFFFFFFFFFFFF)
 LOOKAHEAD = 64

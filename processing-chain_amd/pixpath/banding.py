@@ -24,7 +24,7 @@ MASK_TILE_ROWS = 32      # kBdMaskRows: rows of a tile of the mask kernel
 MASK_TILE_COLS = 64      # kBdMaskCols: its columns
 TILE = 32                # kBdTile: rows and columns of a tile of the contrast kernel
 CHUNK = 4                # kBdChunk: tiles a workgroup walks before it adds its bins
-FRAMES_PER_LAUNCH = 256  # kBdIdx
+FRAMES_PER_LAUNCH = 256  # kFrameMap (csrc/analysis_host.hpp)
 
 
 def default_window(w, h):

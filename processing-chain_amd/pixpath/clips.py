@@ -96,6 +96,12 @@ def clip_batches(path, batch, crop=None, crop_from="yuv422p", what="clip", read=
         rd.close()
 
 
+def nan_mean(v):
+    """The mean of the entries of an array that are not NaN; NaN if none."""
+    v = v[~np.isnan(v)]
+    return float(v.mean()) if v.size else float("nan")
+
+
 def json_value(v):
     """A result for JSON: NaN and the infinities become null."""
     if isinstance(v, (bool, np.bool_)):

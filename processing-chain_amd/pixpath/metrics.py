@@ -13,7 +13,7 @@ import os
 import numpy as np
 
 from . import formats
-from .clips import clip_batches, crop_window, json_value, planar_format  # noqa: F401
+from .clips import clip_batches, crop_window, json_value, nan_mean, planar_format  # noqa: F401
 
 PLANES = ("y", "u", "v")
 # kernel geometry (csrc/metrics.hip), for tests that place sizes on its seams
@@ -85,9 +85,7 @@ def summarize(sse, ssim, fmt, w, h, matched=None, ms_terms=None, vif_terms=None,
             m = m[matched]
         mean["mse_" + name] = float(m.mean()) if m.size else float("nan")
         mean["psnr_" + name] = float(_psnr(mean["mse_" + name], peak))
-        s = res["ssim_" + name]
-        s = s[~np.isnan(s)]
-        mean["ssim_" + name] = float(s.mean()) if s.size else float("nan")
+        mean["ssim_" + name] = nan_mean(res["ssim_" + name])
     res["mean"] = mean
     res["frames"] = int(sse.shape[0])
     if ms_terms is not None:
@@ -117,8 +115,7 @@ def summarize(sse, ssim, fmt, w, h, matched=None, ms_terms=None, vif_terms=None,
             if matched is not None:
                 v[~matched] = np.nan
             res[key] = v
-            ok = v[~np.isnan(v)]
-            mean[key] = float(ok.mean()) if ok.size else float("nan")
+            mean[key] = nan_mean(v)
     return res
 
 

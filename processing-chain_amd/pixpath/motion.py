@@ -10,6 +10,8 @@ recalled; parity with libvmaf is unpinned (DESIGN.md).
 """
 import numpy as np
 
+from .clips import nan_mean
+
 SAD_ABSENT = (1 << 64) - 1  # pp_motion's sad without a previous frame, or of a plane under 3 x 3
 TAPS = (3571, 16004, 26386, 16004, 3571)  # sum 65536
 MIN_SIZE = 3           # the smallest width and height one reflection serves
@@ -20,7 +22,7 @@ TILE_PIECES = 62       # kMoPieces: pieces of a row that are a tile's outputs
 WAVE_ROWS = 16         # kMoLaneRows: rows of a tile one wave owns
 TILE_ROWS = 64         # kMoTileRows: rows of a tile
 SEGMENT = 4            # kMoSeg: shown frames a workgroup walks with the blurred tile in registers
-FRAMES_PER_LAUNCH = 256  # kMoIdx
+FRAMES_PER_LAUNCH = 256  # kFrameMap (csrc/analysis_host.hpp)
 
 
 def tile_cols(bitdepth):
@@ -68,11 +70,7 @@ def summarize(sad, w, h, matched=None):
         m[un] = np.nan
         m2[un] = np.nan
     res = {"motion_y": m, "motion2_y": m2}
-
-    def mean(v):
-        v = v[~np.isnan(v)]
-        return float(v.mean()) if v.size else float("nan")
-    res["mean"] = {"motion_y": mean(m), "motion2_y": mean(m2)}
+    res["mean"] = {"motion_y": nan_mean(m), "motion2_y": nan_mean(m2)}
     return res
 
 

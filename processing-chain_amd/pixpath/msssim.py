@@ -8,6 +8,8 @@ is unpinned (DESIGN.md).
 """
 import numpy as np
 
+from .clips import nan_mean
+
 SCALES = 5
 EXPONENTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
 WINDOW = 11        # kMsTaps: side of the Gaussian window
@@ -17,7 +19,7 @@ MIN_SIZE = WINDOW << (SCALES - 1)  # 176: the smallest width and height with a w
 TILE_COLS = 256    # kMsTileCols: window columns of a workgroup's tile, one per lane
 WAVE_COLS = 64     # of one wave
 BAND_ROWS = 64     # kMsBandRows: window rows of a tile
-FRAMES_PER_LAUNCH = 256  # kMsIdx
+FRAMES_PER_LAUNCH = 256  # kFrameMap (csrc/analysis_host.hpp)
 
 
 def window():
@@ -52,9 +54,5 @@ def summarize(terms, matched=None):
         t[~np.asarray(matched, dtype=bool)] = np.nan
     res = {"ms_ssim_y": pool(t).reshape(-1), "ssim_gauss_y": t[:, 0, 1].copy(),
            "cs_scales_y": t[:, :, 0].copy(), "ssim_scales_y": t[:, :, 1].copy()}
-    mean = {}
-    for key in ("ms_ssim_y", "ssim_gauss_y"):
-        v = res[key][~np.isnan(res[key])]
-        mean[key] = float(v.mean()) if v.size else float("nan")
-    res["mean"] = mean
+    res["mean"] = {key: nan_mean(res[key]) for key in ("ms_ssim_y", "ssim_gauss_y")}
     return res

@@ -375,18 +375,66 @@ def frame_stats(batch, prev=None, want_sad=True, stream=None):
     return hist, sad, over
 
 
-def _luma(x):
+def _luma(x, who):
     """([N, H, W] luma tensor, bit depth) of a FrameBatch or of such a tensor
-    (uint8: 8 bits, uint16: the 10-bit container)."""
+    (uint8: 8 bits, uint16: the 10-bit container) for the operation ``who``."""
     if hasattr(x, "planes"):
         if x.fmt.packed:
-            raise ValueError("sse_band takes planar frames: unpack %s first (ops.unpack)" % x.fmt.name)
+            raise ValueError("%s takes planar frames: unpack %s first (ops.unpack)" % (who, x.fmt.name))
         return x.view(0), x.fmt.depth
     if x.dim() != 3 or (x.shape[2] > 1 and x.stride(2) != 1):
         raise ValueError("luma must be [N, H, W] with contiguous rows")
     if x.dtype not in (torch.uint8, torch.uint16):
         raise ValueError("luma must be uint8 or uint16")
     return x, 8 if x.dtype == torch.uint8 else 10
+
+
+def _luma_pair(ref_batch, dist_batch, who):
+    """(ref luma, dist luma, bit depth) of two batches of one size and depth."""
+    r, rd = _luma(ref_batch, who)
+    d, dd = _luma(dist_batch, who)
+    if rd != dd or tuple(r.shape[1:]) != tuple(d.shape[1:]):
+        raise ValueError("ref and dist differ in bit depth or size")
+    if r.device != d.device:
+        raise ValueError("ref and dist are on different devices")
+    return r, d, dd
+
+
+def _ref_dist(who, entry, ref_batch, dist_batch, ref_index, tail, stream):
+    """The (ref, dist, ref_index) family: the operation ``who`` calls the
+    library's ``entry`` and returns its float64 [ndist, *tail] on the device."""
+    r, d, dd = _luma_pair(ref_batch, dist_batch, who)
+    n, h, w = d.shape
+    idx = None
+    if ref_index is not None:
+        idx = np.ascontiguousarray(ref_index, dtype=np.int32)
+        if idx.shape != (n,):
+            raise ValueError("ref_index needs one entry per dist frame")
+    out = torch.empty((n,) + tail, dtype=torch.float64, device=d.device)
+    if n == 0:  # an empty batch has no data pointer to pass
+        return out
+    es = d.element_size()
+    ctx = context(d.device.index)
+    rp = r.data_ptr() if r.shape[0] else d.data_ptr()  # an empty reference: the call rejects the map
+    check(getattr(lib(), entry)(ctx.handle, dd, w, h, ctypes.c_void_p(rp), r.stride(1) * es, r.stride(0) * es,
+                                r.shape[0], ctypes.c_void_p(d.data_ptr()), d.stride(1) * es, d.stride(0) * es, n,
+                                None if idx is None else idx.ctypes.data, ctypes.c_void_p(out.data_ptr()),
+                                _stream(d, stream)))
+    return out
+
+
+def _sequence(s, index, tail, dtype):
+    """The (sequence, index) family, for the luma ``s``: (index as int32 or
+    None, the result [n, *tail] to fill, n the shown frames)."""
+    idx = None
+    n = s.shape[0]
+    if index is not None:
+        idx = np.ascontiguousarray(index, dtype=np.int32).reshape(-1)
+        n = int(idx.shape[0])
+    out = torch.empty((n,) + tail, dtype=dtype, device=s.device)
+    if n and s.shape[0] == 0:
+        raise ValueError("index names frames of an empty batch")
+    return idx, out
 
 
 def sse_band(ref_batch, dist_batch, first, ncand, stream=None):
@@ -398,12 +446,7 @@ def sse_band(ref_batch, dist_batch, first, ncand, stream=None):
     [ndist, ncand] on the current stream: out[k, c] = sum (dist[k] -
     ref[first[k] + c])^2, exact, or -1 (the kernel's UINT64_MAX read as int64:
     absent) where first[k] + c is no frame of ``ref_batch``."""
-    r, rd = _luma(ref_batch)
-    d, dd = _luma(dist_batch)
-    if rd != dd or tuple(r.shape[1:]) != tuple(d.shape[1:]):
-        raise ValueError("ref and dist differ in bit depth or size")
-    if r.device != d.device:
-        raise ValueError("ref and dist are on different devices")
+    r, d, dd = _luma_pair(ref_batch, dist_batch, "sse_band")
     n, h, w = d.shape
     fi = np.ascontiguousarray(first, dtype=np.int32)
     if fi.shape != (n,):
@@ -433,29 +476,7 @@ def ms_ssim(ref_batch, dist_batch, ref_index=None, stream=None):
     Returns a device tensor float64 [ndist, 5, 2] on the current stream:
     out[k, s, 0] the mean cs and out[k, s, 1] the mean l * cs of scale s, NaN
     for a scale without a window.  pixpath.msssim.pool turns it into MS-SSIM."""
-    r, rd = _luma(ref_batch)
-    d, dd = _luma(dist_batch)
-    if rd != dd or tuple(r.shape[1:]) != tuple(d.shape[1:]):
-        raise ValueError("ref and dist differ in bit depth or size")
-    if r.device != d.device:
-        raise ValueError("ref and dist are on different devices")
-    n, h, w = d.shape
-    idx = None
-    if ref_index is not None:
-        idx = np.ascontiguousarray(ref_index, dtype=np.int32)
-        if idx.shape != (n,):
-            raise ValueError("ref_index needs one entry per dist frame")
-    out = torch.empty((n, 5, 2), dtype=torch.float64, device=d.device)
-    if n == 0:  # an empty batch has no data pointer to pass
-        return out
-    es = d.element_size()
-    ctx = context(d.device.index)
-    rp = r.data_ptr() if r.shape[0] else d.data_ptr()  # an empty reference: the call rejects the map
-    check(lib().pp_ms_ssim(ctx.handle, dd, w, h, ctypes.c_void_p(rp), r.stride(1) * es, r.stride(0) * es, r.shape[0],
-                           ctypes.c_void_p(d.data_ptr()), d.stride(1) * es, d.stride(0) * es, n,
-                           None if idx is None else idx.ctypes.data, ctypes.c_void_p(out.data_ptr()),
-                           _stream(d, stream)))
-    return out
+    return _ref_dist("ms_ssim", "pp_ms_ssim", ref_batch, dist_batch, ref_index, (5, 2), stream)
 
 
 def vif(ref_batch, dist_batch, ref_index=None, stream=None):
@@ -467,29 +488,7 @@ def vif(ref_batch, dist_batch, ref_index=None, stream=None):
     num and out[k, s, 1] the sum of den over the positions of scale s, NaN for
     a scale that does not exist.  pixpath.vif.pool turns it into the per-scale
     ratios and VIF."""
-    r, rd = _luma(ref_batch)
-    d, dd = _luma(dist_batch)
-    if rd != dd or tuple(r.shape[1:]) != tuple(d.shape[1:]):
-        raise ValueError("ref and dist differ in bit depth or size")
-    if r.device != d.device:
-        raise ValueError("ref and dist are on different devices")
-    n, h, w = d.shape
-    idx = None
-    if ref_index is not None:
-        idx = np.ascontiguousarray(ref_index, dtype=np.int32)
-        if idx.shape != (n,):
-            raise ValueError("ref_index needs one entry per dist frame")
-    out = torch.empty((n, 4, 2), dtype=torch.float64, device=d.device)
-    if n == 0:  # an empty batch has no data pointer to pass
-        return out
-    es = d.element_size()
-    ctx = context(d.device.index)
-    rp = r.data_ptr() if r.shape[0] else d.data_ptr()  # an empty reference: the call rejects the map
-    check(lib().pp_vif(ctx.handle, dd, w, h, ctypes.c_void_p(rp), r.stride(1) * es, r.stride(0) * es, r.shape[0],
-                       ctypes.c_void_p(d.data_ptr()), d.stride(1) * es, d.stride(0) * es, n,
-                       None if idx is None else idx.ctypes.data, ctypes.c_void_p(out.data_ptr()),
-                       _stream(d, stream)))
-    return out
+    return _ref_dist("vif", "pp_vif", ref_batch, dist_batch, ref_index, (4, 2), stream)
 
 
 def adm(ref_batch, dist_batch, ref_index=None, stream=None):
@@ -502,29 +501,7 @@ def adm(ref_batch, dist_batch, ref_index=None, stream=None):
     sums of the cubed weighted reference coefficients over the region of scale
     s, NaN for a scale that does not exist.  pixpath.adm.pool turns it into
     adm_scale0..3 and adm2."""
-    r, rd = _luma(ref_batch)
-    d, dd = _luma(dist_batch)
-    if rd != dd or tuple(r.shape[1:]) != tuple(d.shape[1:]):
-        raise ValueError("ref and dist differ in bit depth or size")
-    if r.device != d.device:
-        raise ValueError("ref and dist are on different devices")
-    n, h, w = d.shape
-    idx = None
-    if ref_index is not None:
-        idx = np.ascontiguousarray(ref_index, dtype=np.int32)
-        if idx.shape != (n,):
-            raise ValueError("ref_index needs one entry per dist frame")
-    out = torch.empty((n, 4, 6), dtype=torch.float64, device=d.device)
-    if n == 0:  # an empty batch has no data pointer to pass
-        return out
-    es = d.element_size()
-    ctx = context(d.device.index)
-    rp = r.data_ptr() if r.shape[0] else d.data_ptr()  # an empty reference: the call rejects the map
-    check(lib().pp_adm(ctx.handle, dd, w, h, ctypes.c_void_p(rp), r.stride(1) * es, r.stride(0) * es, r.shape[0],
-                       ctypes.c_void_p(d.data_ptr()), d.stride(1) * es, d.stride(0) * es, n,
-                       None if idx is None else idx.ctypes.data, ctypes.c_void_p(out.data_ptr()),
-                       _stream(d, stream)))
-    return out
+    return _ref_dist("adm", "pp_adm", ref_batch, dist_batch, ref_index, (4, 6), stream)
 
 
 def motion(batch_or_luma, bitdepth=None, index=None, prev=None, stream=None):
@@ -538,23 +515,17 @@ def motion(batch_or_luma, bitdepth=None, index=None, prev=None, stream=None):
     sad[k] = sum |B(frame k) - B(frame k - 1)| over the plane, exact; sad[0]
     without ``prev``, and every entry of a plane under 3 x 3, is 2^64 - 1 =
     absent.  pixpath.motion.pool turns it into motion and motion2."""
-    s, sd = _luma(batch_or_luma)
+    s, sd = _luma(batch_or_luma, "motion")
     d = sd if bitdepth is None else int(bitdepth)
-    nsrc, h, w = s.shape
-    idx = None
-    n = nsrc
-    if index is not None:
-        idx = np.ascontiguousarray(index, dtype=np.int32).reshape(-1)
-        n = int(idx.shape[0])
-    out = torch.empty((n,), dtype=torch.uint64, device=s.device)
+    idx, out = _sequence(s, index, (), torch.uint64)
+    n = out.shape[0]
     if n == 0:  # an empty sequence has no data pointer to pass
         return out
-    if nsrc == 0:
-        raise ValueError("index names frames of an empty batch")
+    nsrc, h, w = s.shape
     es = s.element_size()
     pp, pls = None, 0
     if prev is not None:
-        p, pd = _luma(prev if hasattr(prev, "planes") or prev.dim() == 3 else prev[None])
+        p, pd = _luma(prev if hasattr(prev, "planes") or prev.dim() == 3 else prev[None], "motion")
         if pd != sd or tuple(p.shape[1:]) != (h, w) or p.shape[0] < 1:
             raise ValueError("prev must be one luma plane of the input's size and bit depth")
         if p.device != s.device:
@@ -580,19 +551,13 @@ def banding(batch_or_luma, bitdepth=None, index=None, window=None, tvi=None, str
     frame k with contrast value q.  pixpath.banding.pool turns it into the
     banding index."""
     from . import banding as _banding
-    s, sd = _luma(batch_or_luma)
+    s, sd = _luma(batch_or_luma, "banding")
     d = sd if bitdepth is None else int(bitdepth)
-    nsrc, h, w = s.shape
-    idx = None
-    n = nsrc
-    if index is not None:
-        idx = np.ascontiguousarray(index, dtype=np.int32).reshape(-1)
-        n = int(idx.shape[0])
-    out = torch.empty((n, _banding.SCALES, _banding.BINS), dtype=torch.uint32, device=s.device)
+    idx, out = _sequence(s, index, (_banding.SCALES, _banding.BINS), torch.uint32)
+    n = out.shape[0]
     if n == 0:  # an empty sequence has no data pointer to pass
         return out
-    if nsrc == 0:
-        raise ValueError("index names frames of an empty batch")
+    nsrc, h, w = s.shape
     win = _banding.default_window(w, h) if window is None else int(window)
     tv = None
     if tvi is not None:

@@ -8,6 +8,8 @@ with libvmaf's float_vif is unpinned.
 """
 import numpy as np
 
+from .clips import nan_mean
+
 SCALES = 4
 TAPS = (17, 9, 5, 3)   # filter length of scale s; sigma = taps / 5
 MIN_SIZE = 16          # the smallest width and height with all four scales
@@ -18,7 +20,7 @@ TILE_COLS = 256        # kVifTileCols: columns of a workgroup's tile, one per la
 WAVE_COLS = 64         # of one wave
 BAND_ROWS = 64         # kVifBandRows: rows of a statistics tile
 DEC_BAND_ROWS = 32     # kVifDecRows: output rows of a decimation tile (its columns: TILE_COLS)
-FRAMES_PER_LAUNCH = 256  # kVifIdx
+FRAMES_PER_LAUNCH = 256  # kFrameMap (csrc/analysis_host.hpp)
 
 
 def window(s):
@@ -67,10 +69,6 @@ def summarize(terms, matched=None):
         t[~np.asarray(matched, dtype=bool)] = np.nan
     scales, vif = pool(t)
     res = {"vif_y": vif.reshape(-1), "vif_scales_y": scales.reshape(-1, SCALES)}
-
-    def mean(v):
-        v = v[~np.isnan(v)]
-        return float(v.mean()) if v.size else float("nan")
-    res["mean"] = {"vif_y": mean(res["vif_y"]),
-                   "vif_scales_y": [mean(res["vif_scales_y"][:, s]) for s in range(SCALES)]}
+    res["mean"] = {"vif_y": nan_mean(res["vif_y"]),
+                   "vif_scales_y": [nan_mean(res["vif_scales_y"][:, s]) for s in range(SCALES)]}
     return res
