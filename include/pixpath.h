@@ -672,6 +672,54 @@ int pp_banding(pp_ctx *ctx, int bitdepth, int w, int h,
                int window, const uint16_t *tvi,
                uint32_t *hist, void *stream);
 
+/* ---- DCT-energy complexity of a luma sequence (spec PP-DCTE-1)
+ * A no-reference content descriptor of a clip, modelled on the texture energy
+ * of the Video Complexity Analyzer (Menon et al., 2022): the weight formula is
+ * VCA's as recalled, the integer transform, its two roundings and the
+ * brightness are this library's own; parity with VCA is unpinned: no VCA exists
+ * to compare with.  The normative text is the header comment of
+ * csrc/dctenergy.hip; in short: bitdepth d of 8 (bytes) or 10 (uint16 LE),
+ * x = min(stored, 2^d - 1) (PP-MOTION-1's rule).  Blocks are the
+ * non-overlapping 32 x 32 squares at multiples of 32 wholly inside the plane:
+ * bx = w / 32, by = h / 32 (floor); the ragged right and bottom remainder is not
+ * analysed.  With the integer tables C (2^14 times the orthonormal 32-point
+ * DCT-II, |C| <= 4096) and W (<= 696) of csrc/dct32_tables.hpp, in signed
+ * 32-bit arithmetic with arithmetic shifts:
+ *   T[i][k] = (sum_n C[k][n] x[i][n] + 2^(d+3)) >> (d + 4)
+ *   Y[l][k] = (sum_i C[l][i] T[i][k] + 2^13) >> 14
+ *   e_b = sum over (l, k) != (0, 0) of W[l][k] |Y[l][k]|,   dc_b = Y[0][0]
+ * (both depths on one scale: four times the orthonormal transform of the 8-bit
+ * picture).  The shown sequence is src[index[0]], .., src[index[n-1]] (index:
+ * HOST array of n entries, NULL = identity, which needs n <= nsrc; an entry
+ * outside [0, nsrc) is PP_ERR_INVALID; repeats and backward steps are allowed).
+ *   out    [n][3] uint64, DEVICE, every element written:
+ *          out[k][0] energy = sum_b e_b, out[k][1] dc = sum_b dc_b,
+ *          out[k][2] tdiff = sum_b |e_b(k) - e_b(k-1)| against the frame shown
+ *          before; tdiff of frame 0 is taken against `prev` (one luma plane of
+ *          the same w, h and bitdepth, pitch prev_linesize), or is UINT64_MAX
+ *          = absent when prev is NULL; a repeated frame gives exactly 0.  With
+ *          w < 32 or h < 32 no block exists and all three are absent.
+ *   blocks [n][by bx] uint64, DEVICE, row-major, may be NULL: the e_b, the
+ *          spatial complexity map; its sum over b is energy.
+ * E = energy / (nb 2^20), h = tdiff / (nb 2^20) and L = dc / (128 nb) (the mean
+ * luma of the covered area on the 8-bit scale; VCA's L is a square root of the
+ * DC) are host arithmetic: pixpath/dctenergy.py `pool`.  Exact integer
+ * arithmetic, no float, no atomics, sums in a fixed order: two runs give the
+ * same bits.  Pitch padding and the ragged remainder never count.  NULL ctx,
+ * src or out, w or h < 1, n or nsrc < 0, a linesize below the row's bytes,
+ * 16-bit samples off the 2-byte grid and a bitdepth other than 8 or 10 are
+ * PP_ERR_INVALID; a plane past the 2 GiB buffer range is PP_ERR_UNSUPPORTED.
+ * Arguments are checked before any HIP call; n == 0 is PP_OK and writes
+ * nothing.  Pointers, linesizes and the frame stride on the 16-B grid take 16-B
+ * loads, anything else element loads with the same results.  The workspace
+ * (16 bytes per block and frame, one frame more than a launch's up to 256)
+ * belongs to the context.  Added without raising PP_ABI_VERSION (still 7). */
+int pp_dct_energy(pp_ctx *ctx, int bitdepth, int w, int h,
+                  const void *src, int64_t src_linesize, int64_t src_frame_stride, int nsrc,
+                  const int32_t *index, int n,
+                  const void *prev, int64_t prev_linesize,
+                  uint64_t *out, uint64_t *blocks, void *stream);
+
 /* ---- host helpers --------------------------------------------------------
  * vf_fps output->input frame map (lib/ffmpeg.py:832-834, :959-961, :1038,
  * :1179): map[k] = input frame shown at output frame k.  Returns the number of

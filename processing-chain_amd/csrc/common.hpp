@@ -119,9 +119,10 @@ struct Ctx {
     // histograms of pp_frame_stats (PP-STATS-1), partials of pp_frame_sse_band
     // (PP-ALIGN-1), pyramids and partials of pp_ms_ssim (PP-MSSSIM-1) and of pp_vif
     // (PP-VIF-1), approximation bands and partials of pp_adm (PP-ADM-1), partials of
-    // pp_motion (PP-MOTION-1), levels of pp_banding (PP-BAND-1).  One each: the nine
-    // may be enqueued on different streams at once.
-    Scratch met, crc, stat, aln, mss, vif, adm, mot, bnd;
+    // pp_motion (PP-MOTION-1), levels of pp_banding (PP-BAND-1), block energies of
+    // pp_dct_energy (PP-DCTE-1).  One each: the ten may be enqueued on different
+    // streams at once.
+    Scratch met, crc, stat, aln, mss, vif, adm, mot, bnd, dct;
 };
 
 } // namespace pp

@@ -23,6 +23,8 @@ the ffmpeg strings they replace).
           --banding adds the banding index of the PVS, of its reference as shown and their difference (spec PP-BAND-1)
   banding the banding index of one clip (spec PP-BAND-1): staircase gradients that PSNR and SSIM do not see;
           --crop WxH [--avpvs-pix-fmt NAME] measures the picture inside a v210 / UYVY CPVS canvas
+  complexity the DCT-energy complexity of one clip (spec PP-DCTE-1): texture energy E, its temporal change h and
+          brightness L over 32 x 32 blocks, modelled on VCA; --crop as banding's
   framecrc FFmpeg's `-f framecrc` listing of a file: one GPU Adler-32 per frame (spec PP-HASH-1);
           --against FILE compares with a listing; `avpvs --framecrc FILE` lists what the writer was given
   stats  what is inside one clip (spec PP-STATS-1): per-plane range, mean, percentiles, used bits,
@@ -769,6 +771,14 @@ def cmd_banding(args):
     return 0
 
 
+def cmd_complexity(args):
+    """The DCT-energy complexity of a file (spec PP-DCTE-1): one JSON line."""
+    from . import dctenergy
+    res = dctenergy.dct_energy_of_file(args.input, batch=args.batch, **_crop_settings(args))
+    print(json.dumps(dctenergy.report(res, args.input, per_frame=args.per_frame)))
+    return 0
+
+
 def _avi(path):
     return str(path).lower().endswith(".avi")
 
@@ -944,6 +954,16 @@ def main(argv=None):
                    help="pixel format of the AVPVS the CPVS was padded from (yuv420p...: rows offset rounded to even)")
     p.add_argument("--batch", type=int, default=32)
     p.set_defaults(fn=cmd_banding)
+
+    p = sub.add_parser("complexity")
+    p.add_argument("input", metavar="INPUT")
+    p.add_argument("--per-frame", action="store_true")
+    p.add_argument("--crop", default=None, metavar="WxH",
+                   help="the input is a v210 / UYVY CPVS: measure the WxH AVPVS picture inside its canvas")
+    p.add_argument("--avpvs-pix-fmt", default=None, metavar="NAME",
+                   help="pixel format of the AVPVS the CPVS was padded from (yuv420p...: rows offset rounded to even)")
+    p.add_argument("--batch", type=int, default=32)
+    p.set_defaults(fn=cmd_complexity)
 
     args = ap.parse_args(argv)
     # GPU FFV1 applies to AVI files (the reference's AVPVS container); Y4M /

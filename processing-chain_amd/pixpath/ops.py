@@ -572,6 +572,44 @@ def banding(batch_or_luma, bitdepth=None, index=None, window=None, tvi=None, str
     return out
 
 
+def dct_energy(batch_or_luma, bitdepth=None, index=None, prev=None, blocks=False, stream=None):
+    """DCT-energy sums of a shown sequence (spec PP-DCTE-1, pp_dct_energy): a
+    FrameBatch or its [N, H, W] luma tensor (any pitches; ``bitdepth``
+    overrides what the input implies).  ``index`` and ``prev``: as
+    ops.motion's.  Returns a device tensor uint64 [n, 3] on the current stream:
+    out[k] = (energy, dc, tdiff) over the whole 32 x 32 blocks of frame k,
+    exact; tdiff[0] without ``prev``, and every entry of a plane under 32 x 32,
+    is 2^64 - 1 = absent.  With ``blocks`` also a uint64 [n, by, bx]: the
+    blocks' energies, the spatial complexity map.  pixpath.dctenergy.pool
+    turns the sums into E, h and L."""
+    from . import dctenergy as _dct
+    s, sd = _luma(batch_or_luma, "dct_energy")
+    d = sd if bitdepth is None else int(bitdepth)
+    idx, out = _sequence(s, index, (3,), torch.uint64)
+    n = out.shape[0]
+    nsrc, h, w = s.shape
+    bx, by = _dct.geometry(w, h)
+    bl = torch.empty((n, by, bx), dtype=torch.uint64, device=s.device) if blocks else None
+    if n == 0:  # an empty sequence has no data pointer to pass
+        return (out, bl) if blocks else out
+    es = s.element_size()
+    pp, pls = None, 0
+    if prev is not None:
+        p, pd = _luma(prev if hasattr(prev, "planes") or prev.dim() == 3 else prev[None], "dct_energy")
+        if pd != sd or tuple(p.shape[1:]) != (h, w) or p.shape[0] < 1:
+            raise ValueError("prev must be one luma plane of the input's size and bit depth")
+        if p.device != s.device:
+            raise ValueError("prev is on another device")
+        pp, pls = ctypes.c_void_p(p.data_ptr()), p.stride(1) * es
+    ctx = context(s.device.index)
+    # a map without a block has no data pointer: NULL, nothing is written
+    bp = ctypes.c_void_p(bl.data_ptr()) if blocks and bx * by else None
+    check(lib().pp_dct_energy(ctx.handle, d, w, h, ctypes.c_void_p(s.data_ptr()), s.stride(1) * es, s.stride(0) * es,
+                              nsrc, None if idx is None else idx.ctypes.data, n, pp, pls,
+                              ctypes.c_void_p(out.data_ptr()), bp, _stream(s, stream)))
+    return (out, bl) if blocks else out
+
+
 def spinner_upload(rgba_frames, f, device=None):
     """Upload an RGBA8 animation [n, h, w, 4] (host) for stall compositing."""
     a = np.ascontiguousarray(rgba_frames, dtype=np.uint8)

@@ -261,8 +261,12 @@ def siti_yaml_entry(si, ti, bitdepth=None, normalize=False):
 
 
 def analyse_src(videofile, ordernum, with_siti=True, src_info=None, stream_sizes=None, reader=None, siti=None,
-                normalize=False, bitdepth=None):
-    """util/SRC_analysis.py:120-147 plus an extra "siti" key.
+                normalize=False, bitdepth=None, with_dct_energy=False, dct_energy=None):
+    """util/SRC_analysis.py:120-147 plus an extra "siti" key and, with
+    ``with_dct_energy`` (off by default), an extra "dct_energy" key (spec
+    PP-DCTE-1: clip values, per-frame lists, bit depth, spec string), measured
+    on the GPU or taken from ``dct_energy`` (dctenergy.dct_energy_of_file's
+    dict, or one with its three per-frame lists and ``bitdepth``).
 
     get_src_info / get_stream_size go through ffprobe exactly as the
     reference's (pixpath.probe); the keys the reference writes come out
@@ -289,6 +293,10 @@ def analyse_src(videofile, ordernum, with_siti=True, src_info=None, stream_sizes
         else:
             si, ti, bitdepth = siti_of_file(videofile, reader=reader, normalize=normalize, with_depth=True)
         ret["siti"] = siti_yaml_entry(si, ti, bitdepth, normalize)
+    if with_dct_energy:
+        from . import dctenergy
+        ret["dct_energy"] = dctenergy.yaml_entry(
+            dct_energy if dct_energy is not None else dctenergy.dct_energy_of_file(videofile, reader=reader))
     yaml_path = videofile + ".yaml"
     with open(yaml_path, "w") as outfile:
         yaml.dump(ret, outfile, default_flow_style=False)
@@ -366,6 +374,20 @@ def siti_from_yaml(src_file, with_depth=False):
     return float(e["si"]), float(e["ti"])
 
 
+def dct_energy_from_yaml(src_file):
+    """(E, h, L) from the "dct_energy" key of <src>.yaml written by analyse_src, or None."""
+    import yaml
+    p = src_file + ".yaml"
+    if not os.path.isfile(p):
+        return None
+    with open(p) as f:
+        e = (yaml.safe_load(f) or {}).get("dct_energy")
+    if not e:
+        return None
+    val = lambda k: float("nan") if e.get(k) is None else float(e[k])
+    return val("dct_energy_y"), val("dct_temporal_y"), val("brightness_y")
+
+
 def _script_dir():
     """The directory of the running script (the reference's
     util/complexity_classification.py when it calls complexity_main, as
@@ -396,6 +418,9 @@ def complexity_parse_args(argv=None, script_dir=None):
     ap.add_argument("--siti-scale", default="native", choices=["native", "8bit"],
                     help="si/ti in raw code values of each SRC's bit depth, or all on the 8-bit scale "
                          "(divided by 2^(bitdepth-8))")
+    ap.add_argument("--dct-energy", default="none", choices=["none", "yaml", "gpu"],
+                    help="dct_e/dct_h/dct_l columns (spec PP-DCTE-1): left out, from <src>.yaml (analyse_src), "
+                         "or measured on the GPU when absent there")
     return ap.parse_args(argv)
 
 
@@ -470,6 +495,18 @@ def complexity_main(argv=None, script_dir=None):
         df["ti"] = [vals[f][1] for f in df["file"]]
         df["siti_bitdepth"] = pd.array([vals[f][2] for f in df["file"]], dtype="Int64")
         df["siti_scale"] = [vals[f][3] for f in df["file"]]
+    if a.dct_energy != "none":  # E, h, L of each SRC (spec PP-DCTE-1), from the same sources as si/ti
+        from . import dctenergy
+        nan = float("nan")
+        dvals = {}
+        for f in df["file"]:
+            v = dct_energy_from_yaml(src_of[f])
+            if v is None and a.dct_energy == "gpu":
+                m = dctenergy.dct_energy_of_file(src_of[f])["mean"]
+                v = (m["dct_energy_y"], m["dct_temporal_y"], m["brightness_y"])
+            dvals[f] = v if v is not None else (nan, nan, nan)
+        for col, i in (("dct_e", 0), ("dct_h", 1), ("dct_l", 2)):
+            df[col] = [dvals[f][i] for f in df["file"]]
     csv_file = os.path.join(a.tmp_dir, a.output_file)
     log.info("Writing complexity data to " + str(csv_file))
     df.to_csv(csv_file, index=False)
