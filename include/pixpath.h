@@ -579,6 +579,48 @@ int pp_adm(pp_ctx *ctx, int bitdepth, int w, int h,
            const void *dist, int64_t dist_linesize, int64_t dist_frame_stride, int ndist,
            const int32_t *ref_index, double *out, void *stream);
 
+/* ---- CIEDE2000 colour difference of a distorted batch against its reference
+ * (spec PP-CIEDE-1) --------------------------------------------
+ * The one measure that reads chroma on a perceptual scale: the CIE's dE00
+ * (Sharma, Wu, Dalal 2005) of every luma position of a frame pair.  ref, dist:
+ * batches of w x h frames of the planar format `fmt` (packed formats:
+ * PP_ERR_INVALID; unpack them first with pp_unpack_execute); pitches and frame
+ * strides may differ.  dist frame k is compared with ref frame ref_index[k]
+ * (HOST array of ndist entries, NULL = identity, which needs ndist <= nref; an
+ * entry outside [0, nref) is PP_ERR_INVALID).  Position (x, y) takes luma[y][x]
+ * and the chroma samples at [y >> vsub][x >> hsub] (nearest, no interpolation;
+ * odd sizes: the ceil-sized chroma planes of pp_plane_bytes), as stored, nothing
+ * masked.  With s = 2^(depth - 8): y' = (Y - 16 s) / (219 s), cb, cr = (U, V -
+ * 128 s) / (224 s) (limited range, samples outside it used as they are); the
+ * BT.709 matrix, each of R, G, B clipped to [0, 1]; the sRGB curve to linear
+ * light; XYZ (D65) over its white; Lab; dE00 with the weights kL, kC, kH (the
+ * CIE's: 1, 1, 1).  Everything is IEEE double in the order DESIGN.md writes.
+ *   out [ndist][2] double, DEVICE, every element written and nothing else:
+ *        out[k][0] = the sum of dE00 over the w h positions of frame k,
+ *        out[k][1] = the largest dE00 of frame k.
+ * delta_e = sum / (w h) and the score min(45 - 20 log10(delta_e), 100) are
+ * host arithmetic: pixpath/ciede.py `pool`.  A pair of equal Y, U and V skips
+ * the maths; its dE00 is exactly 0 either way, so identical frames give 0.0
+ * and 0.0.  Two runs give the same bits (no atomics, partials added in a fixed
+ * order), and the layout of the same samples (pitches, pointers or strides on
+ * or off the 16-byte grid) cannot change a bit of the result.  Pitch padding
+ * never counts.  NULL ctx, ref, dist or out, a packed or unknown format, w or
+ * h < 1, ndist or nref < 0, a null plane, a linesize below the row's bytes,
+ * 16-bit samples off the 2-byte grid and a weight that is not positive and
+ * finite are PP_ERR_INVALID; a plane past the 2 GiB buffer range is
+ * PP_ERR_UNSUPPORTED.  Arguments are checked before any HIP call; ndist == 0
+ * is PP_OK and writes nothing.  The partials workspace (16 bytes per unit of
+ * 64 chroma pieces x 16 chroma rows) belongs to the context.  Modelled on
+ * libvmaf's `ciede` feature as recalled (which is recalled to use other
+ * weights, hence the parameters); parity with it is unpinned: no libvmaf
+ * exists to compare with.  Added without raising PP_ABI_VERSION (still 7). */
+int pp_ciede(pp_ctx *ctx, int fmt, int w, int h,
+             const pp_frames *ref, const pp_frames *dist,
+             const int32_t *ref_index, int nref, int ndist,
+             double kL, double kC, double kH,
+             double *out /* DEVICE, ndist x 2: sum, max */,
+             void *stream);
+
 /* ---- VMAF-style motion of a luma sequence (spec PP-MOTION-1) --
  * The temporal feature VMAF calls motion / motion2: every shown frame's luma
  * is blurred with the separable integer filter f = {3571, 16004, 26386, 16004,

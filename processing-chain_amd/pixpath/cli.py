@@ -20,7 +20,9 @@ the ffmpeg strings they replace).
           --adm adds the luma ADM (adm2) and its four per-scale values (spec PP-ADM-1);
           --motion adds motion and motion2 of the reference frames as shown (spec PP-MOTION-1);
           --vmaf-features implies the three and adds the six-value feature vector a VMAF model takes;
-          --banding adds the banding index of the PVS, of its reference as shown and their difference (spec PP-BAND-1)
+          --banding adds the banding index of the PVS, of its reference as shown and their difference (spec PP-BAND-1);
+          --ciede [--ciede-weights KL,KC,KH] adds the CIEDE2000 colour difference over all three planes
+          (spec PP-CIEDE-1): delta_e, delta_e_max and ciede2000
   banding the banding index of one clip (spec PP-BAND-1): staircase gradients that PSNR and SSIM do not see;
           --crop WxH [--avpvs-pix-fmt NAME] measures the picture inside a v210 / UYVY CPVS canvas
   complexity the DCT-energy complexity of one clip (spec PP-DCTE-1): texture energy E, its temporal change h and
@@ -687,6 +689,16 @@ def cmd_metrics(args):
         kw["banding"] = True
     if args.vmaf_features:  # the six elementary features of the published VMAF models; no model is applied
         kw.update(vif=True, adm=True, motion=True)
+    if args.ciede:  # the CIEDE2000 colour difference over all three planes as well (spec PP-CIEDE-1)
+        kw["ciede"] = True
+        if args.ciede_weights:
+            from . import ciede
+            try:
+                kw["ciede_weights"] = ciede.parse_weights(args.ciede_weights)
+            except ValueError as e:
+                raise SystemExit("--ciede-weights: %s" % e)
+    elif args.ciede_weights:
+        raise SystemExit("--ciede-weights needs --ciede")
     res = metrics.metrics_of_files(args.ref, args.input, batch=args.batch, flags=args.flags, **kw)
     out = metrics.report(res, args.ref, args.input, per_frame=args.per_frame)
     if args.vmaf_features:
@@ -901,6 +913,11 @@ def main(argv=None):
     p.add_argument("--vmaf-features", action="store_true",
                    help="implies --vif --adm --motion; add the feature vector adm2, motion2, vif_scale0..3 "
                         "(vmaf_features, vmaf_feature_names; with --per-frame vmaf_features_frames)")
+    p.add_argument("--ciede", action="store_true",
+                   help="add the CIEDE2000 colour difference over all three planes: delta_e, delta_e_max, ciede2000 "
+                        "(spec PP-CIEDE-1); --vmaf-features does not imply it")
+    p.add_argument("--ciede-weights", default=None, metavar="KL,KC,KH",
+                   help="with --ciede: the weights of the lightness, chroma and hue terms (1,1,1)")
     p.set_defaults(fn=cmd_metrics)
 
     p = sub.add_parser("align")

@@ -33,7 +33,7 @@ def _psnr(mse, peak):
 
 
 def summarize(sse, ssim, fmt, w, h, matched=None, ms_terms=None, vif_terms=None, adm_terms=None,
-              motion_terms=None, banding_terms=None):
+              motion_terms=None, banding_terms=None, ciede_terms=None):
     """Host side of PP-METRIC-1: per-frame arrays ``mse_y/u/v/all``,
     ``psnr_y/u/v/all``, ``ssim_y/u/v/all`` (float64 [N]) from pp_metrics' sums
     (sse [N, 3] integers, ssim [N, 3]), plus ``mean``: the clip values (mean
@@ -55,7 +55,10 @@ def summarize(sse, ssim, fmt, w, h, matched=None, ms_terms=None, vif_terms=None,
     (motion.summarize).  ``banding_terms`` (pp_banding's [N, 5, 1024] of the
     distorted frames and of the reference frames as shown, spec PP-BAND-1; only
     when asked for): adds ``banding_y``, ``banding_ref_y`` and their difference
-    ``banding_added_y`` [N] and their clip means (banding.pool)."""
+    ``banding_added_y`` [N] and their clip means (banding.pool).
+    ``ciede_terms`` (pp_ciede's [N, 2], spec PP-CIEDE-1; only when asked for):
+    adds ``delta_e``, ``delta_e_max`` and ``ciede2000`` [N] and their clip
+    values (ciede.summarize)."""
     f = formats.fmt(fmt)
     sse = np.asarray(sse).reshape(-1, 3)
     ssim = np.asarray(ssim, dtype=np.float64).reshape(-1, 3)
@@ -116,6 +119,11 @@ def summarize(sse, ssim, fmt, w, h, matched=None, ms_terms=None, vif_terms=None,
                 v[~matched] = np.nan
             res[key] = v
             mean[key] = nan_mean(v)
+    if ciede_terms is not None:
+        from . import ciede
+        ce = ciede.summarize(ciede_terms, w, h, matched)
+        mean.update(ce.pop("mean"))
+        res.update(ce)
     return res
 
 
@@ -131,7 +139,8 @@ def _map_entries(k0, n, in_rate, out_rate, n_in=None):
 
 
 def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, crop_from="yuv422p", ref_index=None,
-                     ms_ssim=False, vif=False, adm=False, motion=False, banding=False):
+                     ms_ssim=False, vif=False, adm=False, motion=False, banding=False, ciede=False,
+                     ciede_weights=None):
     """PP-METRIC-1 of the file ``dist_path`` (the PVS) against ``ref_path``
     (the SRC); returns ``summarize``'s dict.  Both are read with the chain's
     own readers (FFV1 AVIs through ffv1.open_avpvs_reader, anything else
@@ -177,7 +186,11 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, 
     reference frame shown with it (spec PP-BAND-1, ops.banding on the resident
     frames with the same frame map, after the scaler; the window is
     banding.default_window of the distorted picture) and their difference,
-    what the chain added."""
+    what the chain added.
+
+    ``ciede``: also the CIEDE2000 colour difference of every frame pair, all
+    three planes (spec PP-CIEDE-1, ops.ciede on the same resident frames);
+    ``ciede_weights``: kL, kC, kH (default: the CIE's 1, 1, 1)."""
     import torch
 
     from . import ops
@@ -194,6 +207,7 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, 
         win, win0, n_ref, ref_end = None, 0, 0, False  # resident reference frames [win0, n_ref), dist geometry
         outs, terms, vterms, aterms, k0 = [], [], [], [], 0
         bterms, brterms = [], []  # PP-BAND-1: histograms of the distorted frames and of the reference frames as shown
+        cterms = []  # PP-CIEDE-1: sum and maximum of every frame pair
         mterms, held = [], None  # PP-MOTION-1: the sums, and a copy of the luma plane of the last frame shown
         explicit = None if ref_index is None else np.asarray(ref_index, dtype=np.int64).reshape(-1)
         last = 0  # explicit map: the reference frame an unmatched distorted frame is read against (and not reported)
@@ -251,6 +265,8 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, 
             if banding:
                 bterms.append(ops.banding(d))
                 brterms.append(ops.banding(win, index=m - win0))
+            if ciede:
+                cterms.append(ops.ciede(win, d, ref_index=m - win0, weights=ciede_weights or (1.0, 1.0, 1.0)))
             k0 += d.n
         torch.cuda.current_stream(dev).synchronize()
     if outs:
@@ -274,11 +290,14 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, 
     if banding:
         from .banding import BINS, SCALES
         bt = tuple(torch.cat(t).cpu().numpy() if t else np.zeros((0, SCALES, BINS), np.uint32) for t in (bterms, brterms))
+    ct = None
+    if ciede:
+        ct = torch.cat(cterms).cpu().numpy() if cterms else np.zeros((0, 2))
     if explicit is None:
         return summarize(sse, ssim, dfmt, dw, dh, ms_terms=ms, vif_terms=vt, adm_terms=at, motion_terms=mt,
-                         banding_terms=bt)
+                         banding_terms=bt, ciede_terms=ct)
     return summarize(sse, ssim, dfmt, dw, dh, matched=explicit[:sse.shape[0]] >= 0, ms_terms=ms, vif_terms=vt,
-                     adm_terms=at, motion_terms=mt, banding_terms=bt)
+                     adm_terms=at, motion_terms=mt, banding_terms=bt, ciede_terms=ct)
 
 
 VMAF_FEATURE_NAMES = ("adm2", "motion2", "vif_scale0", "vif_scale1", "vif_scale2", "vif_scale3")
@@ -314,7 +333,9 @@ def report(res, ref_path, dist_path, per_frame=False):
     ``motion_y`` and ``motion2_y`` and, per frame, ``motion_y_frames`` and
     ``motion2_y_frames``.  A result with banding (summarize's banding_terms)
     adds ``banding_y``, ``banding_ref_y`` and ``banding_added_y`` and, per
-    frame, the three lists with ``_frames``."""
+    frame, the three lists with ``_frames``.  A result with CIEDE2000
+    (summarize's ciede_terms) adds ``delta_e``, ``delta_e_max`` and
+    ``ciede2000`` and, per frame, the three lists with ``_frames``."""
     out = {"ref": os.path.basename(ref_path), "file": os.path.basename(dist_path), "frames": int(res["frames"]),
            "spec": "PP-METRIC-1"}
     for k, v in res["mean"].items():
@@ -341,4 +362,7 @@ def report(res, ref_path, dist_path, per_frame=False):
         if "banding_y" in res:
             for key in ("banding_y", "banding_ref_y", "banding_added_y"):
                 out[key + "_frames"] = [json_value(v) for v in res[key]]
+        if "delta_e" in res:
+            from . import ciede
+            out.update(ciede.frames_report(res))
     return out

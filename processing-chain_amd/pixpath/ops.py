@@ -504,6 +504,40 @@ def adm(ref_batch, dist_batch, ref_index=None, stream=None):
     return _ref_dist("adm", "pp_adm", ref_batch, dist_batch, ref_index, (4, 6), stream)
 
 
+def ciede(ref, dist, fmt=None, ref_index=None, weights=(1, 1, 1), stream=None):
+    """Per-frame CIEDE2000 sums of ``dist`` against ``ref`` (spec PP-CIEDE-1,
+    pp_ciede): two FrameBatches of one planar format and size, any pitches.
+    ``fmt`` (a name, an id or a format; default: the batches' own) must be the
+    format both carry.  Distorted frame k is compared with reference frame
+    ``ref_index[k]`` (default: k).  ``weights``: kL, kC, kH (the CIE's 1, 1, 1).
+    Returns a device tensor float64 [ndist, 2] on the current stream: out[k, 0]
+    the sum of dE00 over the w h luma positions and out[k, 1] the largest.
+    pixpath.ciede.pool turns it into delta_e, delta_e_max and ciede2000."""
+    f = dist.fmt if fmt is None else formats.fmt(fmt)
+    if f.packed:
+        raise ValueError("ciede takes planar frames: unpack %s first (ops.unpack)" % f.name)
+    if (ref.fmt.id, ref.w, ref.h) != (f.id, dist.w, dist.h) or dist.fmt.id != f.id:
+        raise ValueError("ref and dist differ in format or size")
+    if ref.device != dist.device:
+        raise ValueError("ref and dist are on different devices")
+    n = dist.n
+    idx = None
+    if ref_index is not None:
+        idx = np.ascontiguousarray(ref_index, dtype=np.int32)
+        if idx.shape != (n,):
+            raise ValueError("ref_index needs one entry per dist frame")
+    kL, kC, kH = (float(v) for v in weights)
+    out = torch.empty((n, 2), dtype=torch.float64, device=dist.device)
+    if n == 0:  # an empty batch has no plane pointers to pass
+        return out
+    ctx = context(dist.device.index)
+    r, d = (ref if ref.n else dist).frames_struct(), dist.frames_struct()  # an empty reference: the call rejects the map
+    check(lib().pp_ciede(ctx.handle, f.id, dist.w, dist.h, ctypes.byref(r), ctypes.byref(d),
+                         None if idx is None else idx.ctypes.data, ref.n, n, kL, kC, kH,
+                         ctypes.c_void_p(out.data_ptr()), _stream(dist.planes[0], stream)))
+    return out
+
+
 def motion(batch_or_luma, bitdepth=None, index=None, prev=None, stream=None):
     """Blurred-luma difference sums of a shown sequence (spec PP-MOTION-1,
     pp_motion): a FrameBatch or its [N, H, W] luma tensor (any pitches;
