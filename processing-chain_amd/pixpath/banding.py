@@ -96,7 +96,7 @@ def banding_of_file(path, batch=32, window=None, crop=None, crop_from="yuv422p")
         window = default_window(w, h) if window is None else int(window)
         outs = [ops.banding(b, window=window) for b in batches]
         torch.cuda.current_stream().synchronize()
-    hist = torch.cat(outs).cpu().numpy() if outs else np.zeros((0, SCALES, BINS), np.uint32)
+    hist = clips.host_array(outs, (SCALES, BINS), np.uint32)
     res = summarize(hist)
     res.update({"frames": int(hist.shape[0]), "w": int(w), "h": int(h), "window": int(window)})
     return res

@@ -12,7 +12,7 @@ libvmaf's ``ciede`` feature is unpinned: no libvmaf exists to compare with
 """
 import numpy as np
 
-from .clips import json_value, nan_mean
+from .clips import nan_mean
 
 SPEC = "PP-CIEDE-1 (CIEDE2000 of BT.709 limited-range Y'CbCr, nearest chroma, parity with libvmaf unpinned)"
 WEIGHTS = (1.0, 1.0, 1.0)   # kL, kC, kH of the CIE
@@ -76,8 +76,3 @@ def summarize(out, w, h, matched=None):
     res["mean"] = {"delta_e": nan_mean(res["delta_e"]), "delta_e_max": float(mx.max()) if mx.size else float("nan"),
                    "ciede2000": nan_mean(res["ciede2000"])}
     return res
-
-
-def frames_report(res):
-    """The per-frame lists of a result for `cli metrics --per-frame`; NaN becomes null."""
-    return {key + "_frames": [json_value(v) for v in res[key]] for key in KEYS}

@@ -661,14 +661,7 @@ def cmd_siti(args):
 
 def cmd_metrics(args):
     from . import metrics
-    kw = {}
-    if args.crop:  # a CPVS canvas: compare the AVPVS picture inside it
-        cw, ch = args.crop.lower().split("x")
-        kw["crop"] = (int(cw), int(ch))
-        if args.avpvs_pix_fmt:
-            kw["crop_from"] = args.avpvs_pix_fmt
-    elif args.avpvs_pix_fmt:
-        raise SystemExit("--avpvs-pix-fmt needs --crop")
+    kw = _crop_settings(args)
     extra = {}
     if args.align:  # pair the frames by their pictures (spec PP-ALIGN-1), not by the vf_fps map
         from . import align
@@ -677,28 +670,19 @@ def cmd_metrics(args):
         extra = {"aligned": True, "unmatched": int((al["map"] < 0).sum())}
     elif args.lookahead is not None or args.min_psnr is not None:
         raise SystemExit("--lookahead and --min-psnr need --align")
-    if args.ms_ssim:  # luma MS-SSIM and Gaussian-window SSIM as well (spec PP-MSSSIM-1)
-        kw["ms_ssim"] = True
-    if args.vif:  # luma VIF and its four per-scale values as well (spec PP-VIF-1)
-        kw["vif"] = True
-    if args.adm:  # luma ADM and its four per-scale values as well (spec PP-ADM-1)
-        kw["adm"] = True
-    if args.motion:  # motion and motion2 of the reference frames as shown as well (spec PP-MOTION-1)
-        kw["motion"] = True
-    if args.banding:  # the banding index of both clips and what the chain added (spec PP-BAND-1)
-        kw["banding"] = True
+    for f in metrics.FEATURES:  # the optional measurements: only the flags that were set are passed on
+        if getattr(args, f.name):
+            kw[f.name] = True
     if args.vmaf_features:  # the six elementary features of the published VMAF models; no model is applied
         kw.update(vif=True, adm=True, motion=True)
-    if args.ciede:  # the CIEDE2000 colour difference over all three planes as well (spec PP-CIEDE-1)
-        kw["ciede"] = True
-        if args.ciede_weights:
-            from . import ciede
-            try:
-                kw["ciede_weights"] = ciede.parse_weights(args.ciede_weights)
-            except ValueError as e:
-                raise SystemExit("--ciede-weights: %s" % e)
-    elif args.ciede_weights:
-        raise SystemExit("--ciede-weights needs --ciede")
+    if args.ciede_weights:
+        if not args.ciede:
+            raise SystemExit("--ciede-weights needs --ciede")
+        from . import ciede
+        try:
+            kw["ciede_weights"] = ciede.parse_weights(args.ciede_weights)
+        except ValueError as e:
+            raise SystemExit("--ciede-weights: %s" % e)
     res = metrics.metrics_of_files(args.ref, args.input, batch=args.batch, flags=args.flags, **kw)
     out = metrics.report(res, args.ref, args.input, per_frame=args.per_frame)
     if args.vmaf_features:
@@ -761,16 +745,8 @@ def cmd_framecrc(args):
 def cmd_stats(args):
     """Per-frame signal statistics of a file (spec PP-STATS-1): one JSON line."""
     from . import stats
-    kw = {}
-    if args.crop:  # a CPVS canvas: analyse the AVPVS picture inside it
-        cw, ch = args.crop.lower().split("x")
-        kw["crop"] = (int(cw), int(ch))
-        if args.avpvs_pix_fmt:
-            kw["crop_from"] = args.avpvs_pix_fmt
-    elif args.avpvs_pix_fmt:
-        raise SystemExit("--avpvs-pix-fmt needs --crop")
     res = stats.stats_of_file(args.input, batch=args.batch, pix_th=args.black_pix_th, pic_th=args.black_pic_th,
-                              histogram=args.histogram, **kw)
+                              histogram=args.histogram, **_crop_settings(args))
     print(json.dumps(stats.report(res, args.input, per_frame=args.per_frame)))
     return 0
 

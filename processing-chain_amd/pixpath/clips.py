@@ -96,6 +96,19 @@ def clip_batches(path, batch, crop=None, crop_from="yuv422p", what="clip", read=
         rd.close()
 
 
+def host_array(outs, tail, dtype):
+    """The per-batch device tensors of a clip as one numpy array [N, *tail] of
+    ``dtype``; of a clip without a frame, the empty array of that shape.
+    uint64 sums, which torch does not concatenate, go through an int64 view
+    (so do int64 tensors that hold the kernel's uint64)."""
+    import torch
+    if not outs:
+        return np.zeros((0,) + tuple(tail), dtype)
+    if np.dtype(dtype) == np.uint64:
+        return torch.cat([o.view(torch.int64) for o in outs]).cpu().numpy().view(np.uint64)
+    return torch.cat(outs).cpu().numpy()
+
+
 def nan_mean(v):
     """The mean of the entries of an array that are not NaN; NaN if none."""
     v = v[~np.isnan(v)]

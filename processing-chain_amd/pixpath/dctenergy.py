@@ -128,12 +128,12 @@ def dct_energy_of_file(videofile, batch=32, reader=None, crop=None, crop_from="y
     try:
         outs, prev = [], None
         for luma in batches:
-            outs.append(ops.dct_energy(luma, depth, prev=prev).view(torch.int64))
+            outs.append(ops.dct_energy(luma, depth, prev=prev))
             prev = luma[luma.shape[0] - 1:].clone()
         torch.cuda.current_stream().synchronize()
     finally:
         rd.close()
-    sums = torch.cat(outs).cpu().numpy().view(np.uint64) if outs else np.zeros((0, 3), np.uint64)
+    sums = clips.host_array(outs, (3,), np.uint64)
     res = summarize(sums, w, h)
     res.update({"frames": int(sums.shape[0]), "w": int(w), "h": int(h), "bitdepth": int(depth),
                 "blocks": geometry(w, h)})

@@ -7,13 +7,19 @@ and vf_ssim and their parity with FFmpeg is unpinned.  The sums
 run on the MI355X (pp_metrics) over the decoded frames both files' readers
 already put into HBM; everything derived from them (MSE, PSNR, the frame and
 clip values) is host arithmetic in this module.
+
+The optional measurements that ride on the same resident frames (MS-SSIM, VIF,
+ADM, motion, banding, CIEDE2000) are the entries of FEATURES: summarize,
+metrics_of_files, report and `cli metrics` loop over that table.
 """
+import collections
 import os
 
 import numpy as np
 
-from . import formats
-from .clips import clip_batches, crop_window, json_value, nan_mean, planar_format  # noqa: F401
+from . import adm as _adm, banding as _banding, ciede as _ciede, formats, motion as _motion, msssim as _msssim, \
+    vif as _vif
+from .clips import clip_batches, crop_window, host_array, json_value, nan_mean, planar_format  # noqa: F401
 
 PLANES = ("y", "u", "v")
 # kernel geometry (csrc/metrics.hip), for tests that place sizes on its seams
@@ -21,6 +27,88 @@ LANE_BYTES = 16   # kMetLaneBytes: bytes a lane loads per row and input
 OWN_LANES = 63    # kMetOwnLanes: lanes of a wave that own blocks
 WAVES = 4         # kMetWaves: waves per workgroup
 BAND_ROWS = 64    # 4 * kBandBlocks: sample rows of a band
+
+
+# One optional measurement of `cli metrics`.
+#   name       the keyword of metrics_of_files that asks for it, and `--name` of `cli metrics`
+#   terms      the keyword of summarize that takes its terms
+#   enqueue    (ops, win, d, idx, carried, options) -> (tensors, carried): one batch's GPU calls.  ``ops``:
+#              pixpath.ops (it needs torch: only metrics_of_files imports it), ``win``: the resident reference
+#              frames, ``d``: the distorted batch, ``idx``: the frame of ``win`` shown with every frame of ``d``,
+#              ``carried``: what the call before returned second (None at first), ``options``: metrics_of_files'
+#              other keywords by name.  ``tensors``: a tuple of device tensors
+#   empty      (trailing shape, dtype) of each of those tensors: what a clip without a frame has
+#   summarize  (terms, w, h, matched) -> the per-frame arrays by key plus ``mean``, the clip values by key.
+#              ``terms``: the host array of the whole clip (a tuple of them where enqueue returns several)
+#   flat, rows the per-frame keys report prints as a list and as a list of rows; flat[0] marks a result that has it
+Feature = collections.namedtuple("Feature", "name terms enqueue empty summarize flat rows")
+
+
+def _frame_pairs(op):
+    """enqueue of a measurement of every frame pair that carries nothing: ops.<op>."""
+    def enqueue(ops, win, d, idx, carried, options):
+        return (getattr(ops, op)(win, d, ref_index=idx),), None
+    return enqueue
+
+
+def _enqueue_motion(ops, win, d, idx, held, options):
+    sad = ops.motion(win, index=idx, prev=held)
+    # the window may be rebuilt before the next batch: a copy, not a view
+    return (sad,), win.view(0)[int(idx[-1]):int(idx[-1]) + 1].clone()
+
+
+def _enqueue_banding(ops, win, d, idx, carried, options):
+    return (ops.banding(d), ops.banding(win, index=idx)), None
+
+
+def _enqueue_ciede(ops, win, d, idx, carried, options):
+    return (ops.ciede(win, d, ref_index=idx, weights=options["ciede_weights"] or _ciede.WEIGHTS),), None
+
+
+def _summarize_banding(terms, w, h, matched):
+    bd, br = (_banding.pool(t)[0] for t in terms)
+    res = {"banding_y": bd, "banding_ref_y": br, "banding_added_y": bd - br}
+    if matched is not None:
+        for v in res.values():
+            v[~matched] = np.nan
+    res["mean"] = {key: nan_mean(v) for key, v in res.items()}
+    return res
+
+
+# In this order: it is the order of the GPU calls of a batch, of the keys of ``mean`` and of the printed line.
+FEATURES = (
+    # The luma MS-SSIM and Gaussian-window SSIM of every frame pair (spec PP-MSSSIM-1, ops.ms_ssim: [N, 5, 2]):
+    # ``ms_ssim_y``, ``ssim_gauss_y`` [N] and their clip means, ``cs_scales_y`` and ``ssim_scales_y`` [N, 5]
+    # (msssim.summarize).
+    Feature("ms_ssim", "ms_terms", _frame_pairs("ms_ssim"), (((5, 2), np.float64),),
+            lambda t, w, h, matched: _msssim.summarize(t, matched),
+            ("ms_ssim_y", "ssim_gauss_y"), ("cs_scales_y", "ssim_scales_y")),
+    # The luma VIF and its four per-scale values of every frame pair (spec PP-VIF-1, ops.vif: [N, 4, 2]):
+    # ``vif_y`` [N] and ``vif_scales_y`` [N, 4] and their clip means (vif.summarize).
+    Feature("vif", "vif_terms", _frame_pairs("vif"), (((4, 2), np.float64),),
+            lambda t, w, h, matched: _vif.summarize(t, matched), ("vif_y",), ("vif_scales_y",)),
+    # The luma ADM (adm2) and its four per-scale values of every frame pair (spec PP-ADM-1, ops.adm: [N, 4, 6]):
+    # ``adm2_y`` [N] and ``adm_scales_y`` [N, 4] and their clip means (adm.summarize).
+    Feature("adm", "adm_terms", _frame_pairs("adm"), (((4, 6), np.float64),), _adm.summarize,
+            ("adm2_y",), ("adm_scales_y",)),
+    # The motion and motion2 of the reference frames as shown (spec PP-MOTION-1, ops.motion on the resident
+    # reference window with the same frame map, after the scaler: uint64 [N]; the luma plane of the last frame a
+    # batch shows is kept as the next batch's ``prev``): ``motion_y`` and ``motion2_y`` [N] and their clip means
+    # (motion.summarize).  An unmatched frame of an explicit map is read against the held reference frame: its
+    # difference is 0 for its neighbours' sake and its own values are NaN.
+    Feature("motion", "motion_terms", _enqueue_motion, (((), np.uint64),), _motion.summarize,
+            ("motion_y", "motion2_y"), ()),
+    # The banding index of every distorted frame, of the reference frame shown with it (spec PP-BAND-1,
+    # ops.banding on the resident frames with the same frame map, after the scaler: two [N, 5, 1024]; the window
+    # is banding.default_window of the distorted picture) and their difference, what the chain added:
+    # ``banding_y``, ``banding_ref_y`` and ``banding_added_y`` [N] and their clip means (banding.pool).
+    Feature("banding", "banding_terms", _enqueue_banding, (((_banding.SCALES, _banding.BINS), np.uint32),) * 2,
+            _summarize_banding, ("banding_y", "banding_ref_y", "banding_added_y"), ()),
+    # The CIEDE2000 colour difference of every frame pair, all three planes (spec PP-CIEDE-1, ops.ciede: [N, 2];
+    # the option ``ciede_weights``: kL, kC, kH, default the CIE's 1, 1, 1): ``delta_e``, ``delta_e_max`` and
+    # ``ciede2000`` [N] and their clip values (ciede.summarize).
+    Feature("ciede", "ciede_terms", _enqueue_ciede, (((2,), np.float64),), _ciede.summarize, _ciede.KEYS, ()),
+)
 
 
 def _psnr(mse, peak):
@@ -42,23 +130,10 @@ def summarize(sse, ssim, fmt, w, h, matched=None, ms_terms=None, vif_terms=None,
     of all planes; SSIM weighted by plane size over the planes whose SSIM is
     defined.  ``matched`` (bool [N], an explicit frame map's): the other frames
     have no reference frame; their rows are NaN and the clip values leave them
-    out.  ``ms_terms`` (pp_ms_ssim's [N, 5, 2], spec PP-MSSSIM-1; only when
-    asked for): adds ``ms_ssim_y``, ``ssim_gauss_y`` [N], ``cs_scales_y`` and
-    ``ssim_scales_y`` [N, 5] and the clip means of the first two
-    (msssim.summarize).  ``vif_terms`` (pp_vif's [N, 4, 2], spec PP-VIF-1; only
-    when asked for): adds ``vif_y`` [N] and ``vif_scales_y`` [N, 4] and their
-    clip means (vif.summarize).  ``adm_terms`` (pp_adm's [N, 4, 6], spec
-    PP-ADM-1; only when asked for): adds ``adm2_y`` [N] and ``adm_scales_y``
-    [N, 4] and their clip means (adm.summarize).  ``motion_terms`` (pp_motion's
-    [N] of the reference frames as shown, spec PP-MOTION-1; only when asked
-    for): adds ``motion_y`` and ``motion2_y`` [N] and their clip means
-    (motion.summarize).  ``banding_terms`` (pp_banding's [N, 5, 1024] of the
-    distorted frames and of the reference frames as shown, spec PP-BAND-1; only
-    when asked for): adds ``banding_y``, ``banding_ref_y`` and their difference
-    ``banding_added_y`` [N] and their clip means (banding.pool).
-    ``ciede_terms`` (pp_ciede's [N, 2], spec PP-CIEDE-1; only when asked for):
-    adds ``delta_e``, ``delta_e_max`` and ``ciede2000`` [N] and their clip
-    values (ciede.summarize)."""
+    out.  Every ``*_terms`` (only when asked for) is the ``terms`` of an entry
+    of FEATURES and adds that entry's per-frame arrays and clip values."""
+    given = {"ms_terms": ms_terms, "vif_terms": vif_terms, "adm_terms": adm_terms, "motion_terms": motion_terms,
+             "banding_terms": banding_terms, "ciede_terms": ciede_terms}
     f = formats.fmt(fmt)
     sse = np.asarray(sse).reshape(-1, 3)
     ssim = np.asarray(ssim, dtype=np.float64).reshape(-1, 3)
@@ -91,39 +166,11 @@ def summarize(sse, ssim, fmt, w, h, matched=None, ms_terms=None, vif_terms=None,
         mean["ssim_" + name] = nan_mean(res["ssim_" + name])
     res["mean"] = mean
     res["frames"] = int(sse.shape[0])
-    if ms_terms is not None:
-        from . import msssim
-        ms = msssim.summarize(ms_terms, matched)
-        mean.update(ms.pop("mean"))
-        res.update(ms)
-    if vif_terms is not None:
-        from . import vif
-        vs = vif.summarize(vif_terms, matched)
-        mean.update(vs.pop("mean"))
-        res.update(vs)
-    if adm_terms is not None:
-        from . import adm
-        ad = adm.summarize(adm_terms, w, h, matched)
-        mean.update(ad.pop("mean"))
-        res.update(ad)
-    if motion_terms is not None:
-        from . import motion
-        mo = motion.summarize(motion_terms, w, h, matched)
-        mean.update(mo.pop("mean"))
-        res.update(mo)
-    if banding_terms is not None:
-        from . import banding
-        bd, br = (banding.pool(t)[0] for t in banding_terms)
-        for key, v in (("banding_y", bd), ("banding_ref_y", br), ("banding_added_y", bd - br)):
-            if matched is not None:
-                v[~matched] = np.nan
-            res[key] = v
-            mean[key] = nan_mean(v)
-    if ciede_terms is not None:
-        from . import ciede
-        ce = ciede.summarize(ciede_terms, w, h, matched)
-        mean.update(ce.pop("mean"))
-        res.update(ce)
+    for feature in FEATURES:
+        if given[feature.terms] is not None:
+            r = feature.summarize(given[feature.terms], w, h, matched)
+            mean.update(r.pop("mean"))
+            res.update(r)
     return res
 
 
@@ -136,6 +183,12 @@ def _map_entries(k0, n, in_rate, out_rate, n_in=None):
     if n_in is None:
         n_in = int((k0 + n) * in_rate / out_rate) + 4
     return ops.fps_map(n_in, in_rate, out_rate)[k0:k0 + n]
+
+
+def _clip_arrays(outs, empty):
+    """The host array of a whole clip for every (trailing shape, dtype) of
+    ``empty``, from the tuples of device tensors its batches gave."""
+    return tuple(host_array([o[i] for o in outs], tail, dtype) for i, (tail, dtype) in enumerate(empty))
 
 
 def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, crop_from="yuv422p", ref_index=None,
@@ -166,35 +219,16 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, 
     values leave it out.  The comparison ends with the shorter of the
     distorted clip and the map.
 
-    ``ms_ssim``: also the luma MS-SSIM and Gaussian-window SSIM of every frame
-    pair (spec PP-MSSSIM-1, ops.ms_ssim on the same resident frames).
-
-    ``vif``: also the luma VIF and its four per-scale values of every frame
-    pair (spec PP-VIF-1, ops.vif on the same resident frames).
-
-    ``adm``: also the luma ADM (adm2) and its four per-scale values of every
-    frame pair (spec PP-ADM-1, ops.adm on the same resident frames).
-
-    ``motion``: also the motion and motion2 of the reference frames as shown
-    (spec PP-MOTION-1, ops.motion on the resident reference window with the
-    same frame map, after the scaler; the luma plane of the last frame shown
-    by a batch is kept as the next batch's ``prev``).  An unmatched frame of
-    an explicit map is read against the held reference frame: its difference
-    is 0 for its neighbours' sake and its own values are NaN.
-
-    ``banding``: also the banding index of every distorted frame, of the
-    reference frame shown with it (spec PP-BAND-1, ops.banding on the resident
-    frames with the same frame map, after the scaler; the window is
-    banding.default_window of the distorted picture) and their difference,
-    what the chain added.
-
-    ``ciede``: also the CIEDE2000 colour difference of every frame pair, all
-    three planes (spec PP-CIEDE-1, ops.ciede on the same resident frames);
-    ``ciede_weights``: kL, kC, kH (default: the CIE's 1, 1, 1)."""
+    ``ms_ssim``, ``vif``, ``adm``, ``motion``, ``banding``, ``ciede``: also
+    the measurement of that ``name`` in FEATURES, on the same resident frames
+    with the same frame map; ``ciede_weights`` is ciede's option."""
     import torch
 
     from . import ops
     from .frames import FrameBatch
+    asked = {"ms_ssim": ms_ssim, "vif": vif, "adm": adm, "motion": motion, "banding": banding, "ciede": ciede}
+    options = {"ciede_weights": ciede_weights}
+    features = [f for f in FEATURES if asked[f.name]]
     batch = int(batch)
     dev = torch.device("cuda", torch.cuda.current_device())
     with clip_batches(ref_path, batch) as (ref, _, refs), \
@@ -205,10 +239,9 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, 
         scaler = None if same else ops.Scaler(rfmt, ref.w, ref.h, dfmt, dw, dh, flags=flags, device=dev)
         in_rate, out_rate = ref.rate, dist.rate
         win, win0, n_ref, ref_end = None, 0, 0, False  # resident reference frames [win0, n_ref), dist geometry
-        outs, terms, vterms, aterms, k0 = [], [], [], [], 0
-        bterms, brterms = [], []  # PP-BAND-1: histograms of the distorted frames and of the reference frames as shown
-        cterms = []  # PP-CIEDE-1: sum and maximum of every frame pair
-        mterms, held = [], None  # PP-MOTION-1: the sums, and a copy of the luma plane of the last frame shown
+        outs, k0 = [], 0
+        fouts = {f.name: [] for f in features}       # what every batch's enqueue returned, by measurement
+        carried = {f.name: None for f in features}   # and what it handed to the next batch's
         explicit = None if ref_index is None else np.asarray(ref_index, dtype=np.int64).reshape(-1)
         last = 0  # explicit map: the reference frame an unmatched distorted frame is read against (and not reported)
         for d in dists:
@@ -251,53 +284,20 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, 
                 break
             if len(m) < d.n:
                 d = FrameBatch(dfmt, dw, dh, len(m), device=d.device, planes=[t[:len(m)] for t in d.planes])
-            outs.append(ops.metrics(win, d, ref_index=m - win0))
-            if ms_ssim:
-                terms.append(ops.ms_ssim(win, d, ref_index=m - win0))
-            if vif:
-                vterms.append(ops.vif(win, d, ref_index=m - win0))
-            if adm:
-                aterms.append(ops.adm(win, d, ref_index=m - win0))
-            if motion:
-                mterms.append(ops.motion(win, index=m - win0, prev=held).view(torch.int64))
-                # the window may be rebuilt before the next batch: a copy, not a view
-                held = win.view(0)[int(m[-1]) - win0:int(m[-1]) - win0 + 1].clone()
-            if banding:
-                bterms.append(ops.banding(d))
-                brterms.append(ops.banding(win, index=m - win0))
-            if ciede:
-                cterms.append(ops.ciede(win, d, ref_index=m - win0, weights=ciede_weights or (1.0, 1.0, 1.0)))
+            idx = m - win0
+            outs.append(ops.metrics(win, d, ref_index=idx))
+            for f in features:
+                tensors, carried[f.name] = f.enqueue(ops, win, d, idx, carried[f.name], options)
+                fouts[f.name].append(tensors)
             k0 += d.n
         torch.cuda.current_stream(dev).synchronize()
-    if outs:
-        sse = torch.cat([o[0] for o in outs]).cpu().numpy()
-        ssim = torch.cat([o[1] for o in outs]).cpu().numpy()
-    else:
-        sse, ssim = np.zeros((0, 3), np.int64), np.zeros((0, 3))
-    ms = None
-    if ms_ssim:
-        ms = torch.cat(terms).cpu().numpy() if terms else np.zeros((0, 5, 2))
-    vt = None
-    if vif:
-        vt = torch.cat(vterms).cpu().numpy() if vterms else np.zeros((0, 4, 2))
-    at = None
-    if adm:
-        at = torch.cat(aterms).cpu().numpy() if aterms else np.zeros((0, 4, 6))
-    mt = None
-    if motion:
-        mt = torch.cat(mterms).cpu().numpy().view(np.uint64) if mterms else np.zeros((0,), np.uint64)
-    bt = None
-    if banding:
-        from .banding import BINS, SCALES
-        bt = tuple(torch.cat(t).cpu().numpy() if t else np.zeros((0, SCALES, BINS), np.uint32) for t in (bterms, brterms))
-    ct = None
-    if ciede:
-        ct = torch.cat(cterms).cpu().numpy() if cterms else np.zeros((0, 2))
-    if explicit is None:
-        return summarize(sse, ssim, dfmt, dw, dh, ms_terms=ms, vif_terms=vt, adm_terms=at, motion_terms=mt,
-                         banding_terms=bt, ciede_terms=ct)
-    return summarize(sse, ssim, dfmt, dw, dh, matched=explicit[:sse.shape[0]] >= 0, ms_terms=ms, vif_terms=vt,
-                     adm_terms=at, motion_terms=mt, banding_terms=bt, ciede_terms=ct)
+    sse, ssim = _clip_arrays(outs, (((3,), np.int64), ((3,), np.float64)))
+    terms = {}
+    for f in features:
+        arrays = _clip_arrays(fouts[f.name], f.empty)
+        terms[f.terms] = arrays[0] if len(arrays) == 1 else arrays
+    matched = None if explicit is None else explicit[:sse.shape[0]] >= 0
+    return summarize(sse, ssim, dfmt, dw, dh, matched=matched, **terms)
 
 
 VMAF_FEATURE_NAMES = ("adm2", "motion2", "vif_scale0", "vif_scale1", "vif_scale2", "vif_scale3")
@@ -322,20 +322,8 @@ def vmaf_features(res, per_frame=False):
 def report(res, ref_path, dist_path, per_frame=False):
     """The JSON object `cli metrics` prints: clip values, and with per_frame
     the per-frame lists; NaN and infinite values become null.  A result with
-    MS-SSIM (summarize's ms_terms) adds ``ms_ssim_y``, ``ssim_gauss_y`` and,
-    per frame, those two and the per-scale means ``cs_scales_y_frames`` /
-    ``ssim_scales_y_frames`` ([N][5]).  A result with VIF (summarize's
-    vif_terms) adds ``vif_y`` and ``vif_scales_y`` (four values) and, per
-    frame, ``vif_y_frames`` and ``vif_scales_y_frames`` ([N][4]).  A result
-    with ADM (summarize's adm_terms) adds ``adm2_y`` and ``adm_scales_y`` (four
-    values) and, per frame, ``adm2_y_frames`` and ``adm_scales_y_frames``
-    ([N][4]).  A result with motion (summarize's motion_terms) adds
-    ``motion_y`` and ``motion2_y`` and, per frame, ``motion_y_frames`` and
-    ``motion2_y_frames``.  A result with banding (summarize's banding_terms)
-    adds ``banding_y``, ``banding_ref_y`` and ``banding_added_y`` and, per
-    frame, the three lists with ``_frames``.  A result with CIEDE2000
-    (summarize's ciede_terms) adds ``delta_e``, ``delta_e_max`` and
-    ``ciede2000`` and, per frame, the three lists with ``_frames``."""
+    a measurement of FEATURES has its clip values among the former and adds
+    its ``flat`` and ``rows`` keys with ``_frames`` to the latter."""
     out = {"ref": os.path.basename(ref_path), "file": os.path.basename(dist_path), "frames": int(res["frames"]),
            "spec": "PP-METRIC-1"}
     for k, v in res["mean"].items():
@@ -345,24 +333,10 @@ def report(res, ref_path, dist_path, per_frame=False):
             for name in PLANES + ("all",):
                 key = "%s_%s" % (kind, name)
                 out[key + "_frames"] = [json_value(v) for v in res[key]]
-        if "ms_ssim_y" in res:
-            for key in ("ms_ssim_y", "ssim_gauss_y"):
-                out[key + "_frames"] = [json_value(v) for v in res[key]]
-            for key in ("cs_scales_y", "ssim_scales_y"):
-                out[key + "_frames"] = [[json_value(v) for v in row] for row in res[key]]
-        if "vif_y" in res:
-            out["vif_y_frames"] = [json_value(v) for v in res["vif_y"]]
-            out["vif_scales_y_frames"] = [[json_value(v) for v in row] for row in res["vif_scales_y"]]
-        if "adm2_y" in res:
-            out["adm2_y_frames"] = [json_value(v) for v in res["adm2_y"]]
-            out["adm_scales_y_frames"] = [[json_value(v) for v in row] for row in res["adm_scales_y"]]
-        if "motion_y" in res:
-            out["motion_y_frames"] = [json_value(v) for v in res["motion_y"]]
-            out["motion2_y_frames"] = [json_value(v) for v in res["motion2_y"]]
-        if "banding_y" in res:
-            for key in ("banding_y", "banding_ref_y", "banding_added_y"):
-                out[key + "_frames"] = [json_value(v) for v in res[key]]
-        if "delta_e" in res:
-            from . import ciede
-            out.update(ciede.frames_report(res))
+        for f in FEATURES:
+            if f.flat[0] in res:
+                for key in f.flat:
+                    out[key + "_frames"] = [json_value(v) for v in res[key]]
+                for key in f.rows:
+                    out[key + "_frames"] = [[json_value(v) for v in row] for row in res[key]]
     return out

@@ -87,10 +87,10 @@ def motion_of_file(path, batch=32, crop=None, crop_from="yuv422p"):
         w, h = (rd.w, rd.h) if window is None else window[2:]
         outs, prev = [], None
         for b in batches:
-            outs.append(ops.motion(b, prev=prev).view(torch.int64))
+            outs.append(ops.motion(b, prev=prev))
             prev = b.view(0)[b.n - 1:b.n].clone()
         torch.cuda.current_stream().synchronize()
-    sad = torch.cat(outs).cpu().numpy().view(np.uint64) if outs else np.zeros((0,), np.uint64)
+    sad = clips.host_array(outs, (), np.uint64)
     res = summarize(sad, w, h)
     res.update({"frames": int(sad.shape[0]), "w": int(w), "h": int(h)})
     return res

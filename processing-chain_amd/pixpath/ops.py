@@ -279,22 +279,48 @@ def siti(luma, bitdepth, prev=None, stream=None, normalize=False):
     return si, ti
 
 
+def _same_frames(ref, dist, f):
+    """Two FrameBatches of the format ``f``, of one size and on one device, or ValueError."""
+    if (ref.fmt.id, ref.w, ref.h) != (f.id, dist.w, dist.h) or dist.fmt.id != f.id:
+        raise ValueError("ref and dist differ in format or size")
+    if ref.device != dist.device:
+        raise ValueError("ref and dist are on different devices")
+
+
+def _ref_index(ref_index, n):
+    """``ref_index`` as a contiguous int32 array with one entry per distorted frame; None stays None."""
+    if ref_index is None:
+        return None
+    idx = np.ascontiguousarray(ref_index, dtype=np.int32)
+    if idx.shape != (n,):
+        raise ValueError("ref_index needs one entry per dist frame")
+    return idx
+
+
+def _prev_plane(prev, s, sd, who):
+    """(pointer, pitch in bytes) of ``prev``, the frame shown before the first
+    of the luma ``s`` of bit depth ``sd``: a FrameBatch, [1, H, W] or [H, W];
+    (None, 0) without one."""
+    if prev is None:
+        return None, 0
+    p, pd = _luma(prev if hasattr(prev, "planes") or prev.dim() == 3 else prev[None], who)
+    if pd != sd or tuple(p.shape[1:]) != tuple(s.shape[1:]) or p.shape[0] < 1:
+        raise ValueError("prev must be one luma plane of the input's size and bit depth")
+    if p.device != s.device:
+        raise ValueError("prev is on another device")
+    return ctypes.c_void_p(p.data_ptr()), p.stride(1) * s.element_size()
+
+
 def metrics(ref, dist, ref_index=None, stream=None):
     """Per-frame, per-plane SSE and SSIM of ``dist`` against ``ref`` (spec
     PP-METRIC-1): two FrameBatches of one planar format and size, any pitches.
     dist frame k is compared with ref frame ``ref_index[k]`` (None: frame k).
     Returns device tensors (sse int64 [N, 3], ssim float64 [N, 3]); the SSIM of
     a plane under 8 samples wide or high is NaN."""
-    if (ref.fmt.id, ref.w, ref.h) != (dist.fmt.id, dist.w, dist.h):
-        raise ValueError("ref and dist differ in format or size")
-    if ref.device != dist.device:
-        raise ValueError("ref and dist are on different devices")
+    _same_frames(ref, dist, dist.fmt)
     n = dist.n
-    ri = None
-    if ref_index is not None:
-        ri = np.ascontiguousarray(ref_index, dtype=np.int32)
-        if ri.shape != (n,):
-            raise ValueError("ref_index needs one entry per dist frame")
+    ri = _ref_index(ref_index, n)
+    if ri is not None:
         if ri.size and ri.max() >= ref.n:
             raise ValueError("ref index out of range")
     elif ref.n < n:
@@ -405,11 +431,7 @@ def _ref_dist(who, entry, ref_batch, dist_batch, ref_index, tail, stream):
     library's ``entry`` and returns its float64 [ndist, *tail] on the device."""
     r, d, dd = _luma_pair(ref_batch, dist_batch, who)
     n, h, w = d.shape
-    idx = None
-    if ref_index is not None:
-        idx = np.ascontiguousarray(ref_index, dtype=np.int32)
-        if idx.shape != (n,):
-            raise ValueError("ref_index needs one entry per dist frame")
+    idx = _ref_index(ref_index, n)
     out = torch.empty((n,) + tail, dtype=torch.float64, device=d.device)
     if n == 0:  # an empty batch has no data pointer to pass
         return out
@@ -516,16 +538,9 @@ def ciede(ref, dist, fmt=None, ref_index=None, weights=(1, 1, 1), stream=None):
     f = dist.fmt if fmt is None else formats.fmt(fmt)
     if f.packed:
         raise ValueError("ciede takes planar frames: unpack %s first (ops.unpack)" % f.name)
-    if (ref.fmt.id, ref.w, ref.h) != (f.id, dist.w, dist.h) or dist.fmt.id != f.id:
-        raise ValueError("ref and dist differ in format or size")
-    if ref.device != dist.device:
-        raise ValueError("ref and dist are on different devices")
+    _same_frames(ref, dist, f)
     n = dist.n
-    idx = None
-    if ref_index is not None:
-        idx = np.ascontiguousarray(ref_index, dtype=np.int32)
-        if idx.shape != (n,):
-            raise ValueError("ref_index needs one entry per dist frame")
+    idx = _ref_index(ref_index, n)
     kL, kC, kH = (float(v) for v in weights)
     out = torch.empty((n, 2), dtype=torch.float64, device=dist.device)
     if n == 0:  # an empty batch has no plane pointers to pass
@@ -557,14 +572,7 @@ def motion(batch_or_luma, bitdepth=None, index=None, prev=None, stream=None):
         return out
     nsrc, h, w = s.shape
     es = s.element_size()
-    pp, pls = None, 0
-    if prev is not None:
-        p, pd = _luma(prev if hasattr(prev, "planes") or prev.dim() == 3 else prev[None], "motion")
-        if pd != sd or tuple(p.shape[1:]) != (h, w) or p.shape[0] < 1:
-            raise ValueError("prev must be one luma plane of the input's size and bit depth")
-        if p.device != s.device:
-            raise ValueError("prev is on another device")
-        pp, pls = ctypes.c_void_p(p.data_ptr()), p.stride(1) * es
+    pp, pls = _prev_plane(prev, s, sd, "motion")
     ctx = context(s.device.index)
     check(lib().pp_motion(ctx.handle, d, w, h, ctypes.c_void_p(s.data_ptr()), s.stride(1) * es, s.stride(0) * es, nsrc,
                           None if idx is None else idx.ctypes.data, n, pp, pls, ctypes.c_void_p(out.data_ptr()),
@@ -627,14 +635,7 @@ def dct_energy(batch_or_luma, bitdepth=None, index=None, prev=None, blocks=False
     if n == 0:  # an empty sequence has no data pointer to pass
         return (out, bl) if blocks else out
     es = s.element_size()
-    pp, pls = None, 0
-    if prev is not None:
-        p, pd = _luma(prev if hasattr(prev, "planes") or prev.dim() == 3 else prev[None], "dct_energy")
-        if pd != sd or tuple(p.shape[1:]) != (h, w) or p.shape[0] < 1:
-            raise ValueError("prev must be one luma plane of the input's size and bit depth")
-        if p.device != s.device:
-            raise ValueError("prev is on another device")
-        pp, pls = ctypes.c_void_p(p.data_ptr()), p.stride(1) * es
+    pp, pls = _prev_plane(prev, s, sd, "dct_energy")
     ctx = context(s.device.index)
     # a map without a block has no data pointer: NULL, nothing is written
     bp = ctypes.c_void_p(bl.data_ptr()) if blocks and bx * by else None

@@ -165,13 +165,9 @@ def arrays_of_file(path, batch=32, crop=None, crop_from="yuv422p"):
             outs.append(ops.frame_stats(b, prev=prev))
             prev = FrameBatch(f, w, h, 1, planes=[t[b.n - 1:b.n] for t in b.planes])
         torch.cuda.current_stream().synchronize()
-    bins = 1 << f.depth
-    if outs:
-        hist = torch.cat([o[0] for o in outs]).cpu().numpy()
-        sad = torch.cat([o[1] for o in outs]).cpu().numpy().view(np.uint64)
-        over = torch.cat([o[2] for o in outs]).cpu().numpy()
-    else:
-        hist, sad, over = np.zeros((0, 3, bins), np.int32), np.zeros((0, 3), np.uint64), np.zeros((0, 3), np.int32)
+    hist = clips.host_array([o[0] for o in outs], (3, 1 << f.depth), np.int32)
+    sad = clips.host_array([o[1] for o in outs], (3,), np.uint64)
+    over = clips.host_array([o[2] for o in outs], (3,), np.int32)
     return hist, sad, over, f, int(w), int(h)
 
 
