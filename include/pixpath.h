@@ -621,6 +621,58 @@ int pp_ciede(pp_ctx *ctx, int fmt, int w, int h,
              double *out /* DEVICE, ndist x 2: sum, max */,
              void *stream);
 
+/* ---- PSNR-HVS and PSNR-HVS-M of a distorted batch against its reference
+ * (spec PP-HVS-1) ------------------------------------------------
+ * The contrast-sensitivity-weighted PSNR over 8 x 8 DCT blocks, without and
+ * with between-coefficient contrast masking, of each of the three planes.
+ * ref, dist: batches of w x h frames of the planar format `fmt` (packed
+ * formats: PP_ERR_INVALID; unpack them first with pp_unpack_execute); pitches
+ * and frame strides may differ.  dist frame k is compared with ref frame
+ * ref_index[k] (HOST array of ndist entries, NULL = identity, which needs
+ * ndist <= nref; an entry outside [0, nref) is PP_ERR_INVALID).  Samples are
+ * used as stored, nothing masked or clipped.  Per plane of pw x ph samples the
+ * blocks have their origins at (i step, j step) for every i, j with origin + 8
+ * <= the plane's size; `step` is 8 (the published definition) or 7 (blocks
+ * overlap by a sample, so that an 8-grid codec's block edges fall inside
+ * blocks); per axis nb(n) = n < 8 ? 0 : (n - 8) / step + 1, and samples right
+ * of or below the last block do not count.  Per block of A (ref) and B (dist):
+ * D(X) the orthonormal 2-D DCT-II, rows first; with Q the JPEG Annex K
+ * luminance table, CSF the published six-decimal contrast-sensitivity table
+ * (25.735088 / Q to 5.5e-7; DESIGN.md prints it) and M = (10 / Q)^2 (the same
+ * tables for all three planes: build-defined, the published measure is for
+ * grey pictures); m = the sum over (k, l) != (0, 0) of D(X)[k][l]^2 M[k][l]; pop =
+ * 21 (sum of V_q of the four 4 x 4 quadrants) / (5 V) in exact 64-bit integers,
+ * V = 64 sum x^2 - (sum x)^2, V_q = 16 sum_q x^2 - (sum_q x)^2, 0 for V = 0;
+ * mask(X) = sqrt(m pop) / 32; T = max(mask(A), mask(B)); u = |D(A) - D(B)|;
+ * S_hvs adds (u CSF)^2 over the 64 coefficients; S_hvsm the same after u =
+ * max(u - T / M, 0) at every coefficient but DC.  Everything floating is IEEE
+ * double in the order DESIGN.md writes.
+ *   out [ndist][3][2] double, DEVICE, every element written and nothing else:
+ *        out[k][p][0] = S_hvs, out[k][p][1] = S_hvsm of plane p (Y, U, V) of
+ *        frame k, summed over its blocks; 0.0, 0.0 for a plane with no block
+ *        (under 8 samples in a direction).
+ * mse = S / (64 blocks), psnr = 10 log10(peak^2 / mse) and the `all` value
+ * from 0.8 mse_y + 0.1 (mse_u + mse_v) are host arithmetic: pixpath/psnrhvs.py
+ * `pool`.  Identical blocks give exactly 0 and 0; S_hvsm <= S_hvs.  Two runs
+ * give the same bits (no atomics, partials added in a fixed order), and the
+ * layout of the same samples (pitches, pointers or strides on or off the
+ * 16-byte grid) cannot change a bit of the result.  Pitch padding never
+ * counts.  NULL ctx, ref, dist or out, a packed or unknown format, w or h < 1,
+ * ndist or nref < 0, a step other than 7 or 8, a null plane, a linesize below
+ * the row's bytes and 16-bit samples off the 2-byte grid are PP_ERR_INVALID; a
+ * plane past the 2 GiB buffer range is PP_ERR_UNSUPPORTED.  Arguments are
+ * checked before any HIP call; ndist == 0 is PP_OK and writes nothing.  The
+ * partials workspace (16 bytes per unit of 32 blocks of a block row) belongs
+ * to the context.  Modelled on Ponomarenko et al. (2007), the published
+ * psnrhvsm definition, and on libvmaf's `psnr_hvs` feature as recalled (step
+ * 7, the 0.8 / 0.1 / 0.1 weighting); parity with both is unpinned: neither
+ * exists to compare with.  Added without raising PP_ABI_VERSION (still 7). */
+int pp_psnr_hvs(pp_ctx *ctx, int fmt, int w, int h,
+                const pp_frames *ref, const pp_frames *dist,
+                const int32_t *ref_index, int nref, int ndist, int step,
+                double *out /* DEVICE, ndist x 3 x 2: per plane S_hvs, S_hvsm */,
+                void *stream);
+
 /* ---- VMAF-style motion of a luma sequence (spec PP-MOTION-1) --
  * The temporal feature VMAF calls motion / motion2: every shown frame's luma
  * is blurred with the separable integer filter f = {3571, 16004, 26386, 16004,

@@ -41,7 +41,7 @@ extern "C" int pp_ctx_create(int device, pp_ctx **out) {
 extern "C" int pp_ctx_destroy(pp_ctx *ctx) {
     if (!ctx) return PP_OK;
     void *const bufs[] = {ctx->spin_buf, ctx->met.buf, ctx->crc.buf, ctx->stat.buf, ctx->aln.buf, ctx->mss.buf,
-                          ctx->vif.buf, ctx->adm.buf, ctx->mot.buf, ctx->bnd.buf, ctx->dct.buf, ctx->cie.buf};
+                          ctx->vif.buf, ctx->adm.buf, ctx->mot.buf, ctx->bnd.buf, ctx->dct.buf, ctx->cie.buf, ctx->hvs.buf};
     bool set = false;  // the device is touched only if there is something to free
     for (void *b : bufs) {
         if (!b) continue;

@@ -120,9 +120,10 @@ struct Ctx {
     // (PP-ALIGN-1), pyramids and partials of pp_ms_ssim (PP-MSSSIM-1) and of pp_vif
     // (PP-VIF-1), approximation bands and partials of pp_adm (PP-ADM-1), partials of
     // pp_motion (PP-MOTION-1), levels of pp_banding (PP-BAND-1), block energies of
-    // pp_dct_energy (PP-DCTE-1), partials of pp_ciede (PP-CIEDE-1).  One each: the
-    // eleven may be enqueued on different streams at once.
-    Scratch met, crc, stat, aln, mss, vif, adm, mot, bnd, dct, cie;
+    // pp_dct_energy (PP-DCTE-1), partials of pp_ciede (PP-CIEDE-1) and of
+    // pp_psnr_hvs (PP-HVS-1).  One each: the twelve may be enqueued on different
+    // streams at once.
+    Scratch met, crc, stat, aln, mss, vif, adm, mot, bnd, dct, cie, hvs;
 };
 
 } // namespace pp

@@ -22,7 +22,9 @@ the ffmpeg strings they replace).
           --vmaf-features implies the three and adds the six-value feature vector a VMAF model takes;
           --banding adds the banding index of the PVS, of its reference as shown and their difference (spec PP-BAND-1);
           --ciede [--ciede-weights KL,KC,KH] adds the CIEDE2000 colour difference over all three planes
-          (spec PP-CIEDE-1): delta_e, delta_e_max and ciede2000
+          (spec PP-CIEDE-1): delta_e, delta_e_max and ciede2000;
+          --psnr-hvs [--hvs-step 7|8] adds PSNR-HVS and PSNR-HVS-M of the three planes and their weighted
+          `all` value over 8 x 8 DCT blocks (spec PP-HVS-1)
   banding the banding index of one clip (spec PP-BAND-1): staircase gradients that PSNR and SSIM do not see;
           --crop WxH [--avpvs-pix-fmt NAME] measures the picture inside a v210 / UYVY CPVS canvas
   complexity the DCT-energy complexity of one clip (spec PP-DCTE-1): texture energy E, its temporal change h and
@@ -683,6 +685,10 @@ def cmd_metrics(args):
             kw["ciede_weights"] = ciede.parse_weights(args.ciede_weights)
         except ValueError as e:
             raise SystemExit("--ciede-weights: %s" % e)
+    if args.hvs_step is not None:
+        if not args.psnr_hvs:
+            raise SystemExit("--hvs-step needs --psnr-hvs")
+        kw["hvs_step"] = args.hvs_step
     res = metrics.metrics_of_files(args.ref, args.input, batch=args.batch, flags=args.flags, **kw)
     out = metrics.report(res, args.ref, args.input, per_frame=args.per_frame)
     if args.vmaf_features:
@@ -894,6 +900,12 @@ def main(argv=None):
                         "(spec PP-CIEDE-1); --vmaf-features does not imply it")
     p.add_argument("--ciede-weights", default=None, metavar="KL,KC,KH",
                    help="with --ciede: the weights of the lightness, chroma and hue terms (1,1,1)")
+    p.add_argument("--psnr-hvs", action="store_true",
+                   help="add PSNR-HVS and PSNR-HVS-M over 8 x 8 DCT blocks of all three planes: mse_hvs_*, mse_hvsm_*, "
+                        "psnr_hvs_*, psnr_hvsm_* for y, u, v, all (spec PP-HVS-1); --vmaf-features does not imply it")
+    p.add_argument("--hvs-step", type=int, choices=(7, 8), default=None, metavar="7|8",
+                   help="with --psnr-hvs: the distance between block origins: 8 (the published definition, default) "
+                        "or 7 (blocks overlap by a sample)")
     p.set_defaults(fn=cmd_metrics)
 
     p = sub.add_parser("align")

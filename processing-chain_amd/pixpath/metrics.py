@@ -9,7 +9,7 @@ already put into HBM; everything derived from them (MSE, PSNR, the frame and
 clip values) is host arithmetic in this module.
 
 The optional measurements that ride on the same resident frames (MS-SSIM, VIF,
-ADM, motion, banding, CIEDE2000) are the entries of FEATURES: summarize,
+ADM, motion, banding, CIEDE2000, PSNR-HVS) are the entries of FEATURES: summarize,
 metrics_of_files, report and `cli metrics` loop over that table.
 """
 import collections
@@ -18,7 +18,7 @@ import os
 import numpy as np
 
 from . import adm as _adm, banding as _banding, ciede as _ciede, formats, motion as _motion, msssim as _msssim, \
-    vif as _vif
+    psnrhvs as _psnrhvs, vif as _vif
 from .clips import clip_batches, crop_window, host_array, json_value, nan_mean, planar_format  # noqa: F401
 
 PLANES = ("y", "u", "v")
@@ -38,8 +38,9 @@ BAND_ROWS = 64    # 4 * kBandBlocks: sample rows of a band
 #              ``carried``: what the call before returned second (None at first), ``options``: metrics_of_files'
 #              other keywords by name.  ``tensors``: a tuple of device tensors
 #   empty      (trailing shape, dtype) of each of those tensors: what a clip without a frame has
-#   summarize  (terms, w, h, matched) -> the per-frame arrays by key plus ``mean``, the clip values by key.
-#              ``terms``: the host array of the whole clip (a tuple of them where enqueue returns several)
+#   summarize  (terms, w, h, matched, fmt, options) -> the per-frame arrays by key plus ``mean``, the clip values by
+#              key.  ``terms``: the host array of the whole clip (a tuple of them where enqueue returns several),
+#              ``fmt``: the frames' format, ``options``: summarize's option keywords by name
 #   flat, rows the per-frame keys report prints as a list and as a list of rows; flat[0] marks a result that has it
 Feature = collections.namedtuple("Feature", "name terms enqueue empty summarize flat rows")
 
@@ -65,7 +66,11 @@ def _enqueue_ciede(ops, win, d, idx, carried, options):
     return (ops.ciede(win, d, ref_index=idx, weights=options["ciede_weights"] or _ciede.WEIGHTS),), None
 
 
-def _summarize_banding(terms, w, h, matched):
+def _enqueue_psnr_hvs(ops, win, d, idx, carried, options):
+    return (ops.psnr_hvs(win, d, ref_index=idx, step=options["hvs_step"] or _psnrhvs.STEPS[0]),), None
+
+
+def _summarize_banding(terms, w, h, matched, fmt, options):
     bd, br = (_banding.pool(t)[0] for t in terms)
     res = {"banding_y": bd, "banding_ref_y": br, "banding_added_y": bd - br}
     if matched is not None:
@@ -81,23 +86,23 @@ FEATURES = (
     # ``ms_ssim_y``, ``ssim_gauss_y`` [N] and their clip means, ``cs_scales_y`` and ``ssim_scales_y`` [N, 5]
     # (msssim.summarize).
     Feature("ms_ssim", "ms_terms", _frame_pairs("ms_ssim"), (((5, 2), np.float64),),
-            lambda t, w, h, matched: _msssim.summarize(t, matched),
+            lambda t, w, h, matched, fmt, options: _msssim.summarize(t, matched),
             ("ms_ssim_y", "ssim_gauss_y"), ("cs_scales_y", "ssim_scales_y")),
     # The luma VIF and its four per-scale values of every frame pair (spec PP-VIF-1, ops.vif: [N, 4, 2]):
     # ``vif_y`` [N] and ``vif_scales_y`` [N, 4] and their clip means (vif.summarize).
     Feature("vif", "vif_terms", _frame_pairs("vif"), (((4, 2), np.float64),),
-            lambda t, w, h, matched: _vif.summarize(t, matched), ("vif_y",), ("vif_scales_y",)),
+            lambda t, w, h, matched, fmt, options: _vif.summarize(t, matched), ("vif_y",), ("vif_scales_y",)),
     # The luma ADM (adm2) and its four per-scale values of every frame pair (spec PP-ADM-1, ops.adm: [N, 4, 6]):
     # ``adm2_y`` [N] and ``adm_scales_y`` [N, 4] and their clip means (adm.summarize).
-    Feature("adm", "adm_terms", _frame_pairs("adm"), (((4, 6), np.float64),), _adm.summarize,
-            ("adm2_y",), ("adm_scales_y",)),
+    Feature("adm", "adm_terms", _frame_pairs("adm"), (((4, 6), np.float64),),
+            lambda t, w, h, matched, fmt, options: _adm.summarize(t, w, h, matched), ("adm2_y",), ("adm_scales_y",)),
     # The motion and motion2 of the reference frames as shown (spec PP-MOTION-1, ops.motion on the resident
     # reference window with the same frame map, after the scaler: uint64 [N]; the luma plane of the last frame a
     # batch shows is kept as the next batch's ``prev``): ``motion_y`` and ``motion2_y`` [N] and their clip means
     # (motion.summarize).  An unmatched frame of an explicit map is read against the held reference frame: its
     # difference is 0 for its neighbours' sake and its own values are NaN.
-    Feature("motion", "motion_terms", _enqueue_motion, (((), np.uint64),), _motion.summarize,
-            ("motion_y", "motion2_y"), ()),
+    Feature("motion", "motion_terms", _enqueue_motion, (((), np.uint64),),
+            lambda t, w, h, matched, fmt, options: _motion.summarize(t, w, h, matched), ("motion_y", "motion2_y"), ()),
     # The banding index of every distorted frame, of the reference frame shown with it (spec PP-BAND-1,
     # ops.banding on the resident frames with the same frame map, after the scaler: two [N, 5, 1024]; the window
     # is banding.default_window of the distorted picture) and their difference, what the chain added:
@@ -107,7 +112,16 @@ FEATURES = (
     # The CIEDE2000 colour difference of every frame pair, all three planes (spec PP-CIEDE-1, ops.ciede: [N, 2];
     # the option ``ciede_weights``: kL, kC, kH, default the CIE's 1, 1, 1): ``delta_e``, ``delta_e_max`` and
     # ``ciede2000`` [N] and their clip values (ciede.summarize).
-    Feature("ciede", "ciede_terms", _enqueue_ciede, (((2,), np.float64),), _ciede.summarize, _ciede.KEYS, ()),
+    Feature("ciede", "ciede_terms", _enqueue_ciede, (((2,), np.float64),),
+            lambda t, w, h, matched, fmt, options: _ciede.summarize(t, w, h, matched), _ciede.KEYS, ()),
+    # PSNR-HVS and PSNR-HVS-M of every frame pair, all three planes (spec PP-HVS-1, ops.psnr_hvs: [N, 3, 2]; the
+    # option ``hvs_step``: 8, the published definition and default, or 7): ``mse_hvs_*``, ``mse_hvsm_*``,
+    # ``psnr_hvs_*`` and ``psnr_hvsm_*`` for y, u, v and all [N] and their clip values, ``hvs_step`` and
+    # ``hvs_blocks`` (psnrhvs.summarize).
+    Feature("psnr_hvs", "hvs_terms", _enqueue_psnr_hvs, (((3, 2), np.float64),),
+            lambda t, w, h, matched, fmt, options: _psnrhvs.summarize(t, w, h, matched, fmt,
+                                                                      options["hvs_step"] or _psnrhvs.STEPS[0]),
+            _psnrhvs.KEYS, ()),
 )
 
 
@@ -121,7 +135,7 @@ def _psnr(mse, peak):
 
 
 def summarize(sse, ssim, fmt, w, h, matched=None, ms_terms=None, vif_terms=None, adm_terms=None,
-              motion_terms=None, banding_terms=None, ciede_terms=None):
+              motion_terms=None, banding_terms=None, ciede_terms=None, hvs_terms=None, hvs_step=None):
     """Host side of PP-METRIC-1: per-frame arrays ``mse_y/u/v/all``,
     ``psnr_y/u/v/all``, ``ssim_y/u/v/all`` (float64 [N]) from pp_metrics' sums
     (sse [N, 3] integers, ssim [N, 3]), plus ``mean``: the clip values (mean
@@ -131,9 +145,11 @@ def summarize(sse, ssim, fmt, w, h, matched=None, ms_terms=None, vif_terms=None,
     defined.  ``matched`` (bool [N], an explicit frame map's): the other frames
     have no reference frame; their rows are NaN and the clip values leave them
     out.  Every ``*_terms`` (only when asked for) is the ``terms`` of an entry
-    of FEATURES and adds that entry's per-frame arrays and clip values."""
+    of FEATURES and adds that entry's per-frame arrays and clip values;
+    ``hvs_step`` is the block step ``hvs_terms`` were taken at (default 8)."""
     given = {"ms_terms": ms_terms, "vif_terms": vif_terms, "adm_terms": adm_terms, "motion_terms": motion_terms,
-             "banding_terms": banding_terms, "ciede_terms": ciede_terms}
+             "banding_terms": banding_terms, "ciede_terms": ciede_terms, "hvs_terms": hvs_terms}
+    options = {"hvs_step": hvs_step}
     f = formats.fmt(fmt)
     sse = np.asarray(sse).reshape(-1, 3)
     ssim = np.asarray(ssim, dtype=np.float64).reshape(-1, 3)
@@ -168,7 +184,7 @@ def summarize(sse, ssim, fmt, w, h, matched=None, ms_terms=None, vif_terms=None,
     res["frames"] = int(sse.shape[0])
     for feature in FEATURES:
         if given[feature.terms] is not None:
-            r = feature.summarize(given[feature.terms], w, h, matched)
+            r = feature.summarize(given[feature.terms], w, h, matched, f, options)
             mean.update(r.pop("mean"))
             res.update(r)
     return res
@@ -193,7 +209,7 @@ def _clip_arrays(outs, empty):
 
 def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, crop_from="yuv422p", ref_index=None,
                      ms_ssim=False, vif=False, adm=False, motion=False, banding=False, ciede=False,
-                     ciede_weights=None):
+                     ciede_weights=None, psnr_hvs=False, hvs_step=None):
     """PP-METRIC-1 of the file ``dist_path`` (the PVS) against ``ref_path``
     (the SRC); returns ``summarize``'s dict.  Both are read with the chain's
     own readers (FFV1 AVIs through ffv1.open_avpvs_reader, anything else
@@ -219,15 +235,19 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, 
     values leave it out.  The comparison ends with the shorter of the
     distorted clip and the map.
 
-    ``ms_ssim``, ``vif``, ``adm``, ``motion``, ``banding``, ``ciede``: also
-    the measurement of that ``name`` in FEATURES, on the same resident frames
-    with the same frame map; ``ciede_weights`` is ciede's option."""
+    ``ms_ssim``, ``vif``, ``adm``, ``motion``, ``banding``, ``ciede``,
+    ``psnr_hvs``: also the measurement of that ``name`` in FEATURES, on the
+    same resident frames with the same frame map; ``ciede_weights`` is ciede's
+    option, ``hvs_step`` (8 or 7) psnr_hvs'."""
     import torch
 
     from . import ops
     from .frames import FrameBatch
-    asked = {"ms_ssim": ms_ssim, "vif": vif, "adm": adm, "motion": motion, "banding": banding, "ciede": ciede}
-    options = {"ciede_weights": ciede_weights}
+    asked = {"ms_ssim": ms_ssim, "vif": vif, "adm": adm, "motion": motion, "banding": banding, "ciede": ciede,
+             "psnr_hvs": psnr_hvs}
+    if hvs_step is not None:
+        _psnrhvs.check_step(hvs_step)
+    options = {"ciede_weights": ciede_weights, "hvs_step": hvs_step}
     features = [f for f in FEATURES if asked[f.name]]
     batch = int(batch)
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -297,6 +317,8 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, 
         arrays = _clip_arrays(fouts[f.name], f.empty)
         terms[f.terms] = arrays[0] if len(arrays) == 1 else arrays
     matched = None if explicit is None else explicit[:sse.shape[0]] >= 0
+    if psnr_hvs:
+        terms["hvs_step"] = hvs_step
     return summarize(sse, ssim, dfmt, dw, dh, matched=matched, **terms)
 
 

@@ -553,6 +553,32 @@ def ciede(ref, dist, fmt=None, ref_index=None, weights=(1, 1, 1), stream=None):
     return out
 
 
+def psnr_hvs(ref, dist, ref_index=None, step=8, stream=None):
+    """Per-frame, per-plane PSNR-HVS / PSNR-HVS-M sums of ``dist`` against
+    ``ref`` (spec PP-HVS-1, pp_psnr_hvs): two FrameBatches of one planar format
+    and size, any pitches.  Distorted frame k is compared with reference frame
+    ``ref_index[k]`` (default: k).  ``step``: 8 (the published definition) or
+    7 (overlapping blocks).  Returns a device tensor float64 [ndist, 3, 2] on
+    the current stream: out[k, p, 0] = S_hvs and out[k, p, 1] = S_hvsm of plane
+    p over its 8 x 8 blocks, 0.0 for a plane with no block.
+    pixpath.psnrhvs.pool turns it into the MSE and PSNR values."""
+    f = dist.fmt
+    if f.packed:
+        raise ValueError("psnr_hvs takes planar frames: unpack %s first (ops.unpack)" % f.name)
+    _same_frames(ref, dist, f)
+    n = dist.n
+    idx = _ref_index(ref_index, n)
+    out = torch.empty((n, 3, 2), dtype=torch.float64, device=dist.device)
+    if n == 0:  # an empty batch has no plane pointers to pass
+        return out
+    ctx = context(dist.device.index)
+    r, d = (ref if ref.n else dist).frames_struct(), dist.frames_struct()  # an empty reference: the call rejects the map
+    check(lib().pp_psnr_hvs(ctx.handle, f.id, dist.w, dist.h, ctypes.byref(r), ctypes.byref(d),
+                            None if idx is None else idx.ctypes.data, ref.n, n, int(step),
+                            ctypes.c_void_p(out.data_ptr()), _stream(dist.planes[0], stream)))
+    return out
+
+
 def motion(batch_or_luma, bitdepth=None, index=None, prev=None, stream=None):
     """Blurred-luma difference sums of a shown sequence (spec PP-MOTION-1,
     pp_motion): a FrameBatch or its [N, H, W] luma tensor (any pitches;
