@@ -341,6 +341,32 @@ int pp_siti(pp_ctx *ctx, int bitdepth, int w, int h, const void *luma,
 int pp_siti_ex(pp_ctx *ctx, int bitdepth, int w, int h, const void *luma,
                int64_t linesize, int64_t frame_stride, int nframes,
                const void *prev, double *si, double *ti, int flags, void *stream);
+/* The launch plan of the SI/TI kernel for `nframes` frames of w x h on `slots`
+ * resident workgroups (csrc/siti_plan.hpp): host only, no context, no GPU.
+ * Writes the first min(n, PP_SITI_PLAN_FIELDS) of
+ *   tiles_x, bands, ntiles, ragged, interior_bands, fchunk, chunks, groups
+ * to out: 1984-px tile columns, 16-row bands, their product, w % 8 != 0 (the
+ * ragged kernel instances), bands whose 18 window rows all lie in the frame,
+ * frames a (chunk, tile) unit walks, chunks (the last may be shorter), and
+ * workgroups launched = min(slots, ntiles * chunks); nframes == 0 plans
+ * fchunk = chunks = groups = 0.  Bad depth or size: the code and message of
+ * pp_siti_ex; slots < 1, nframes < 0, out == NULL or n < 1: PP_ERR_INVALID.
+ * Added without raising PP_ABI_VERSION (still 7). */
+#define PP_SITI_PLAN_FIELDS 8
+int pp_siti_plan(int bitdepth, int w, int h, int nframes, int slots,
+                 int32_t *out, int n);
+/* pp_siti_ex planned for `slots` resident workgroups instead of the device's
+ * own count (CUs x occupancy): slots == 0 asks the device, so
+ * pp_siti_ex(...) == pp_siti_slots(..., flags, 0, stream); slots < 0 is
+ * PP_ERR_INVALID.  Any positive count is a legal launch (the grid never exceeds
+ * the units) and the results do not depend on it, bit for bit: the plan decides
+ * which workgroup computes a partial, never its arithmetic.  For tests, which
+ * force small clips onto every arm of the kernel with it.  Added without
+ * raising PP_ABI_VERSION (still 7). */
+int pp_siti_slots(pp_ctx *ctx, int bitdepth, int w, int h, const void *luma,
+                  int64_t linesize, int64_t frame_stride, int nframes,
+                  const void *prev, double *si, double *ti, int flags, int slots,
+                  void *stream);
 
 /* ---- full-reference PSNR / SSIM (spec PP-METRIC-1) --------
  * New feature after p03_generateAvPvs.py: how far an AVPVS is from its SRC,

@@ -28,7 +28,11 @@
 //     ffv1_decode_kernel read it: every slice inside its stream's 64-byte
 //     aligned window of the packet buffer, the GOP triples tiling the frames
 //     stream by stream, a continued GOP only where states were carried; a
-//     refused one names its stream and says why.
+//     refused one names its stream and says why;
+//   * the SI/TI launch planner (siti_plan.hpp siti_plan): random widths,
+//     heights, frame and slot counts, small and huge -- the chunks cover the
+//     frames with only the last one short, the grid is min(slots, units) >= 1,
+//     and the interior band count is that of the band condition.
 //
 //   * general FFV1 records given as seeds (file of u32-LE-length-prefixed
 //     records: the oracle's FFmpeg-like records with transmitted state
@@ -48,6 +52,7 @@
 #include "ffv1host.hpp"
 #include "filters.hpp"
 #include "scale_plan.hpp"
+#include "siti_plan.hpp"
 
 namespace pp {
 // the library's error sink (api.cpp in the product build)
@@ -778,6 +783,40 @@ long fuzz_groups(Rng &r, int iters, long *ok) {
     return n;
 }
 
+// ---- SI/TI launch plans (siti_plan.hpp) ---------------------------------------
+long fuzz_siti_plans(Rng &r, int iters) {
+    long n = 0;
+    for (int it = 0; it < iters; ++it) {
+        // sizes and counts small (every value near the tile, band and lane edges) and up to the ABI's int range
+        // (heights to 100000 rows: the planner counts the bands one by one)
+        auto pick = [&r](int small, int big) { return r.below(4) ? 1 + r.below(small) : 1 + r.below(big); };
+        const int w = 2 + pick(4100, 0x7ffffff0), h = 2 + pick(70, 100000), nf = pick(40, 0x7ffffff0);
+        const int64_t slots = r.below(8) ? pick(70, 4096) : pick(0x7ffffff0, 0x7ffffff0);
+        if ((int64_t)((w + kSpan - 1) / kSpan) * ((h + kBand - 1) / kBand) > 0x7fffffff) continue;  // ntiles is an int
+        const SitiPlan p = siti_plan(1 + r.below(2), w, h, nf, slots);
+        ++n;
+        char tag[96];
+        std::snprintf(tag, sizeof tag, "siti plan %dx%d x%d on %lld", w, h, nf, (long long)slots);
+        PCHECK(p.tiles_x == (w + kSpan - 1) / kSpan && p.bands == (h + kBand - 1) / kBand &&
+                   p.ntiles == p.tiles_x * p.bands && p.ragged == (w % kLanePx != 0),
+               "geometry %d x %d = %d, ragged %d", p.tiles_x, p.bands, p.ntiles, p.ragged);
+        // every band but the first and the last has a row above and a row below its 16
+        const int interior = std::max(0, p.bands - 2);
+        PCHECK(p.interior_bands == interior && !siti_band_interior(0, h), "%d interior bands, expected %d",
+               p.interior_bands, interior);
+        PCHECK(p.fchunk >= 1 && p.fchunk <= nf, "fchunk %d", p.fchunk);
+        if (p.fchunk < 1) continue;
+        PCHECK((int64_t)(p.chunks - 1) * p.fchunk < nf && (int64_t)p.chunks * p.fchunk >= nf, "%d chunks of %d", p.chunks,
+               p.fchunk);
+        PCHECK(p.groups >= 1 && p.groups == std::min<int64_t>(slots, (int64_t)p.ntiles * p.chunks), "%d groups", p.groups);
+    }
+    // no frames, no slots: the geometry alone / one slot
+    const SitiPlan e = siti_plan(2, 1985, 34, 0, 4), o = siti_plan(2, 1985, 34, 9, 0), o1 = siti_plan(2, 1985, 34, 9, 1);
+    CHECK(e.ntiles == 6 && e.fchunk == 0 && e.chunks == 0 && e.groups == 0, "plan of no frames");
+    CHECK(o.fchunk == o1.fchunk && o.chunks == o1.chunks && o.groups == 1, "plan on no slots");
+    return n;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -792,7 +831,9 @@ int main(int argc, char **argv) {
     const long f = fuzz_plans(r, iters / 60);
     long groups_ok = 0;
     const long g = fuzz_groups(r, iters / 10, &groups_ok);
-    std::printf("records %ld packets %ld scans %ld filters %ld seeded %ld plans %ld groups %ld groups_ok %ld failures %d\n",
-                a, b, c, d, e, f, g, groups_ok, g_fail);
+    const long h = fuzz_siti_plans(r, iters);
+    std::printf("records %ld packets %ld scans %ld filters %ld seeded %ld plans %ld groups %ld groups_ok %ld "
+                "siti_plans %ld failures %d\n",
+                a, b, c, d, e, f, g, groups_ok, h, g_fail);
     return g_fail ? 1 : 0;
 }

@@ -38,13 +38,10 @@
 
 #include "common.hpp"
 #include "device.hpp"
+#include "siti_plan.hpp"  // kBand, kLanePx, kWaveSpan, kSpan; the launch plan
 
 namespace pp {
 
-constexpr int kBand = 16;
-constexpr int kLanePx = 8;
-constexpr int kWaveSpan = 62 * kLanePx;  // 496 px per wave: lanes 0 and 63 are halo lanes
-constexpr int kSpan = 4 * kWaveSpan;     // 1984 px per workgroup
 constexpr int kOob = kOobOff;
 
 struct SitiPartial {
@@ -456,7 +453,8 @@ __device__ __forceinline__ void siti_range(const uint8_t *frames, int64_t ls, in
 // any moment hold vertically adjacent bands of the SAME frames, and with the
 // XCD-aware numbering (consecutive L on one XCD) a band's two halo rows are
 // read from HBM by one neighbour and hit that XCD's L2 for the other.  The
-// host picks fchunk so that the rounds of units fill the slots (see pp_siti).
+// host picks fchunk so that the rounds of units fill the slots: siti_plan in
+// siti_plan.hpp, which pp_siti_plan reports and pp_siti_slots launches.
 template <typename T, bool RAGGED>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void siti_kernel(
     const uint8_t *frames, int64_t ls, int64_t fs, int nframes, const uint8_t *prev, int W, int H, int tiles_x,
@@ -468,7 +466,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void s
         const int tile = (int)(u - (int64_t)chunk * ntiles);
         const int f0 = chunk * fchunk, f1 = min(nframes, f0 + fchunk);
         const int y0 = tile / tiles_x * kBand;
-        if (y0 >= 1 && y0 + kBand + 1 <= H)
+        if (y0 >= 1 && y0 + kBand + 1 <= H)  // siti_band_interior (siti_plan.hpp), spelled out: see there
             siti_range<T, true, RAGGED>(frames, ls, fs, prev, W, H, tiles_x, tile, f0, f1, part);
         else
             siti_range<T, false, RAGGED>(frames, ls, fs, prev, W, H, tiles_x, tile, f0, f1, part);
@@ -524,48 +522,58 @@ extern "C" int pp_siti(pp_ctx *ctx, int bitdepth, int w, int h, const void *luma
     return pp_siti_ex(ctx, bitdepth, w, h, luma, linesize, frame_stride, nframes, prev, si, ti, 0, stream);
 }
 
+// bit depth and frame size, as every SI/TI entry checks them
+static int siti_check_shape(int bitdepth, int w, int h) {
+    if (bitdepth != 8 && bitdepth != 10) PP_FAIL(PP_ERR_INVALID, "bit depth %d (8 or 10)", bitdepth);
+    if (w < 3 || h < 3) PP_FAIL(PP_ERR_INVALID, "frame %dx%d too small for Sobel", w, h);
+    return PP_OK;
+}
+
 extern "C" int pp_siti_ex(pp_ctx *ctx, int bitdepth, int w, int h, const void *luma, int64_t linesize,
                           int64_t frame_stride, int nframes, const void *prev, double *si, double *ti, int flags,
                           void *stream) {
+    return pp_siti_slots(ctx, bitdepth, w, h, luma, linesize, frame_stride, nframes, prev, si, ti, flags, 0, stream);
+}
+
+extern "C" int pp_siti_plan(int bitdepth, int w, int h, int nframes, int slots, int32_t *out, int n) {
+    if (!out || n < 1 || nframes < 0) PP_FAIL(PP_ERR_INVALID, "null argument");
+    if (const int rc = siti_check_shape(bitdepth, w, h)) return rc;
+    if (slots < 1) PP_FAIL(PP_ERR_INVALID, "siti slots %d", slots);
+    const SitiPlan p = siti_plan(bitdepth > 8 ? 2 : 1, w, h, nframes, slots);
+    const int32_t v[PP_SITI_PLAN_FIELDS] = {p.tiles_x,        p.bands,  p.ntiles, p.ragged,
+                                            p.interior_bands, p.fchunk, p.chunks, p.groups};
+    for (int i = 0; i < std::min(n, PP_SITI_PLAN_FIELDS); ++i) out[i] = v[i];
+    return PP_OK;
+}
+
+extern "C" int pp_siti_slots(pp_ctx *ctx, int bitdepth, int w, int h, const void *luma, int64_t linesize,
+                             int64_t frame_stride, int nframes, const void *prev, double *si, double *ti, int flags,
+                             int slots_arg, void *stream) {
     if (flags & ~PP_SITI_NORMALIZE) PP_FAIL(PP_ERR_INVALID, "siti flags 0x%x", flags);
     if (!ctx || !luma || !si || !ti || nframes < 0) PP_FAIL(PP_ERR_INVALID, "null argument");
-    if (bitdepth != 8 && bitdepth != 10) PP_FAIL(PP_ERR_INVALID, "bit depth %d (8 or 10)", bitdepth);
-    if (w < 3 || h < 3) PP_FAIL(PP_ERR_INVALID, "frame %dx%d too small for Sobel", w, h);
+    if (const int rc = siti_check_shape(bitdepth, w, h)) return rc;
+    if (slots_arg < 0) PP_FAIL(PP_ERR_INVALID, "siti slots %d", slots_arg);
     if (nframes == 0) return PP_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
     PP_HIP(hipSetDevice(ctx->device));
     const int bytes = bitdepth > 8 ? 2 : 1;
-    const int tiles_x = (w + kSpan - 1) / kSpan;
-    const int bands = (h + kBand - 1) / kBand;
-    const int ntiles = tiles_x * bands;
     const bool ragged = (w % kLanePx) != 0;
     using KFn = void (*)(const uint8_t *, int64_t, int64_t, int, const uint8_t *, int, int, int, int, int,
                          SitiPartial *);
     const KFn k = bytes == 2 ? (ragged ? siti_kernel<uint16_t, true> : siti_kernel<uint16_t, false>)
                              : (ragged ? siti_kernel<uint8_t, true> : siti_kernel<uint8_t, false>);
-    const void *kfn = reinterpret_cast<const void *>(k);
-    // one wave of resident workgroups (a partial second wave would idle most of
-    // the chip), each walking an equal share of the (tile, frame) units
-    int dev_cus = 0, per_cu = 0;
-    PP_HIP(hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
-    PP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, 256, 0));
-    const int64_t slots = std::max(1, dev_cus * std::max(1, per_cu));
-    // frames per chunk: for R = 1..8 rounds of units over the slots, the
-    // longest chunk that still fits R rounds; keep the R with the shortest
-    // makespan (R * fchunk frames, plus ~1 frame of pipeline fill per round)
-    int fchunk = nframes;
-    {
-        double best = 1e300;
-        for (int R = 1; R <= 8; ++R) {
-            const int K = (int)std::max<int64_t>(1, std::min<int64_t>(nframes, R * slots / ntiles));
-            const int fc = (nframes + K - 1) / K;
-            const int64_t units = (int64_t)ntiles * ((nframes + fc - 1) / fc);
-            const int64_t rounds = (units + std::min(slots, units) - 1) / std::min(slots, units);
-            const double cost = (double)rounds * (fc + 1);
-            if (cost < best) { best = cost; fchunk = fc; }
-        }
+    // the resident workgroup slots of this device, unless the caller gives a
+    // count (tests force small plans with it; any positive count is a legal
+    // launch, groups never exceeds the units)
+    int64_t slots = slots_arg;
+    if (slots_arg == 0) {
+        int dev_cus = 0, per_cu = 0;
+        PP_HIP(hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+        PP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(k), 256, 0));
+        slots = std::max(1, dev_cus * std::max(1, per_cu));
     }
-    const int groups = (int)std::min<int64_t>(slots, (int64_t)ntiles * ((nframes + fchunk - 1) / fchunk));
+    const SitiPlan plan = siti_plan(bytes, w, h, nframes, slots);
+    const int tiles_x = plan.tiles_x, ntiles = plan.ntiles, fchunk = plan.fchunk, groups = plan.groups;
     // The kernel reads each lane's 8 pixels as one 16-B (8-B) buffer load, so
     // rows must start on that granule; other layouts (odd widths packed
     // contiguously, views into a row) are first repacked on the device into a

@@ -17,7 +17,7 @@ EXPORTS = (
     "pp_abi_version", "pp_last_error", "pp_ctx_create", "pp_ctx_destroy", "pp_plane_bytes",
     "pp_v210_linesize", "pp_scale_plan_create", "pp_scale_chain_plan_create", "pp_scale_plan_destroy", "pp_scale_plan_filter",
     "pp_scale_plan_path", "pp_scale_plan_stats", "pp_scale_plan_instances", "pp_scale_execute", "pp_pad_execute", "pp_v210_pack", "pp_cpvs_execute", "pp_unpack_execute", "pp_spinner_upload", "pp_stall_compose",
-    "pp_siti", "pp_siti_ex", "pp_metrics", "pp_frame_adler32", "pp_frame_stats", "pp_frame_sse_band", "pp_ms_ssim", "pp_vif", "pp_adm", "pp_ciede", "pp_psnr_hvs", "pp_motion", "pp_banding", "pp_dct_energy", "pp_pack_arms", "pp_fps_map",
+    "pp_siti", "pp_siti_ex", "pp_siti_plan", "pp_siti_slots", "pp_metrics", "pp_frame_adler32", "pp_frame_stats", "pp_frame_sse_band", "pp_ms_ssim", "pp_vif", "pp_adm", "pp_ciede", "pp_psnr_hvs", "pp_motion", "pp_banding", "pp_dct_energy", "pp_pack_arms", "pp_fps_map",
     "pp_device_alloc", "pp_device_free", "pp_host_alloc", "pp_host_free", "pp_stream_create",
     "pp_stream_destroy", "pp_stream_synchronize", "pp_event_create", "pp_event_destroy", "pp_event_record",
     "pp_stream_wait_event", "pp_event_synchronize", "pp_event_elapsed_ms", "pp_copy_async", "pp_copy2d_async",
@@ -92,6 +92,8 @@ def lib():
         "pp_stall_compose": (i32, [vp, i32, i32, i32, fr, vp, vp, fr, i32, vp]),
         "pp_siti": (i32, [vp, i32, i32, i32, vp, i64, i64, i32, vp, vp, vp, vp]),
         "pp_siti_ex": (i32, [vp, i32, i32, i32, vp, i64, i64, i32, vp, vp, vp, i32, vp]),
+        "pp_siti_plan": (i32, [i32, i32, i32, i32, i32, ctypes.POINTER(ctypes.c_int32), i32]),
+        "pp_siti_slots": (i32, [vp, i32, i32, i32, vp, i64, i64, i32, vp, vp, vp, i32, i32, vp]),
         "pp_metrics": (i32, [vp, i32, i32, i32, fr, fr, vp, i32, vp, vp, vp]),
         "pp_frame_adler32": (i32, [vp, i32, i32, i32, fr, i32, ctypes.c_uint32, vp, vp]),
         "pp_frame_stats": (i32, [vp, i32, i32, i32, fr, i32, fr, vp, vp, vp, vp]),

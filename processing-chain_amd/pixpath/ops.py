@@ -254,11 +254,27 @@ def unpack(src, crop=None, luma_only=False, dst=None, stream=None):
     return dst
 
 
-def siti(luma, bitdepth, prev=None, stream=None, normalize=False):
+SitiPlan = collections.namedtuple("SitiPlan", "tiles_x bands ntiles ragged interior_bands fchunk chunks groups")
+
+
+def siti_plan(bitdepth, w, h, nframes, slots):
+    """The launch plan of the SI/TI kernel for ``nframes`` frames of w x h on
+    ``slots`` resident workgroups (pp_siti_plan): host only, no GPU.  A depth
+    or size pp_siti refuses raises its PixpathError."""
+    out = (ctypes.c_int32 * len(SitiPlan._fields))()
+    check(lib().pp_siti_plan(int(bitdepth), int(w), int(h), int(nframes), int(slots), out, len(out)))
+    p = SitiPlan(*out)
+    return p._replace(ragged=bool(p.ragged))
+
+
+def siti(luma, bitdepth, prev=None, stream=None, normalize=False, *, slots=None):
     """Per-frame P.910 SI/TI of a [N, H, W] luma tensor (uint8 / uint16, may be a
     pitched view).  Returns two float64 device tensors [N]; ti[0] is NaN when
     ``prev`` (the frame before luma[0]) is not given.  ``normalize``: values
-    divided by 2^(bitdepth-8) (the 8-bit scale, PP_SITI_NORMALIZE)."""
+    divided by 2^(bitdepth-8) (the 8-bit scale, PP_SITI_NORMALIZE).  ``slots``:
+    plan the launch for that many resident workgroups instead of the device's
+    own count (pp_siti_slots; tests force small clips onto every arm of the
+    kernel with it); the results do not depend on it."""
     if luma.dim() != 3:
         raise ValueError("luma must be [N, H, W]")
     n, h, w = luma.shape
@@ -268,14 +284,17 @@ def siti(luma, bitdepth, prev=None, stream=None, normalize=False):
     ctx = context(luma.device.index)
     si = torch.empty(n, dtype=torch.float64, device=luma.device)
     ti = torch.empty(n, dtype=torch.float64, device=luma.device)
+    if n == 0:  # an empty tensor has no address to hand over
+        return si, ti
     pp = None
     if prev is not None:
         if prev.stride(-1) != 1 or prev.stride(-2) != luma.stride(1):
             raise ValueError("prev must share the luma row pitch")
         pp = ctypes.c_void_p(prev.data_ptr())
-    check(lib().pp_siti_ex(ctx.handle, int(bitdepth), w, h, ctypes.c_void_p(luma.data_ptr()), luma.stride(1) * es,
-                           luma.stride(0) * es, n, pp, ctypes.c_void_p(si.data_ptr()),
-                           ctypes.c_void_p(ti.data_ptr()), 1 if normalize else 0, _stream(luma, stream)))
+    check(lib().pp_siti_slots(ctx.handle, int(bitdepth), w, h, ctypes.c_void_p(luma.data_ptr()), luma.stride(1) * es,
+                              luma.stride(0) * es, n, pp, ctypes.c_void_p(si.data_ptr()),
+                              ctypes.c_void_p(ti.data_ptr()), 1 if normalize else 0, 0 if slots is None else int(slots),
+                              _stream(luma, stream)))
     return si, ti
 
 
