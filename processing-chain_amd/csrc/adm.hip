@@ -35,7 +35,6 @@
 // bits.
 #include <algorithm>
 #include <cmath>
-#include <cstring>
 
 #include "analysis_dev.hpp"
 #include "analysis_host.hpp"
@@ -243,22 +242,15 @@ extern "C" int pp_adm(pp_ctx *ctx, int bitdepth, int w, int h, const void *ref, 
                       int64_t ref_frame_stride, int nref, const void *dist, int64_t dist_linesize,
                       int64_t dist_frame_stride, int ndist, const int32_t *ref_index, double *out, void *stream) {
     if (!ctx || !ref || !dist || !out) PP_FAIL(PP_ERR_INVALID, "null argument");
+    const LumaClip r{ref, ref_linesize, ref_frame_stride, nref}, d{dist, dist_linesize, dist_frame_stride, ndist};
     LumaPlanes lp;
-    if (int e = luma_open(lp, bitdepth, w, h)) return e;
-    if (ndist < 0) PP_FAIL(PP_ERR_INVALID, "ndist %d < 0", ndist);
-    if (nref < 0) PP_FAIL(PP_ERR_INVALID, "nref %d < 0", nref);
-    if (int e = luma_plane(lp, ref, ref_linesize, ref_frame_stride, "ref ")) return e;
-    if (int e = luma_plane(lp, dist, dist_linesize, dist_frame_stride, "dist ")) return e;
-    if (int e = luma_close(lp)) return e;  // one element-wise path: lp.aligned is not looked at
-    if (int e = check_frame_map(ref_index, ndist, nref, kRefIndexMap)) return e;
+    // one element-wise path: lp.aligned is not looked at
+    if (int e = luma_checks(lp, bitdepth, w, h, r, d, false, ref_index, ndist, kRefIndexMap)) return e;
     const int es = lp.es;
     if (ndist == 0) return PP_OK;
 
     AdmArgs a{};
-    a.ref = static_cast<const uint8_t *>(ref);
-    a.dist = static_cast<const uint8_t *>(dist);
-    a.rls = ref_linesize; a.rfs = ref_frame_stride;
-    a.dls = dist_linesize; a.dfs = dist_frame_stride;
+    put_luma_pair(a, r, d);
     a.mul = 1.0 / (double)(1 << (bitdepth - 8));
     // the Daubechies-2 analysis pair, in fp64 (PP-ADM-1)
     const double r3 = std::sqrt(3.0), nrm = 4.0 * std::sqrt(2.0);
@@ -303,10 +295,10 @@ extern "C" int pp_adm(pp_ctx *ctx, int bitdepth, int w, int h, const void *ref, 
 
     // a workgroup per tile: far below 2^31 for planes inside the 2 GiB range and kFrameMap frames
     auto grid = [](int64_t n) { return dim3((unsigned)n); };
-    for (int k0 = 0; k0 < ndist; k0 += per) {
+    each_launch(ndist, per, [&](int k0, int nk) {
         AdmArgs b = a;
-        b.nk = std::min(per, ndist - k0);
-        for (int k = 0; k < b.nk; ++k) b.idx[k] = ref_index ? ref_index[k0 + k] : k0 + k;
+        b.nk = nk;
+        fill_map(b.idx, ref_index, k0, nk);
         b.dist += (int64_t)k0 * a.dfs;
         b.out = out + (int64_t)k0 * kAdmScales * kAdmSums;
         for (int s = 0; s < a.nsc; ++s) {
@@ -318,7 +310,7 @@ extern "C" int pp_adm(pp_ctx *ctx, int bitdepth, int w, int h, const void *ref, 
             else hipLaunchKernelGGL((adm_scale<double, 3>), gr, dim3(kAdmLanes), 0, st, b);
         }
         hipLaunchKernelGGL(adm_finalize, dim3((b.nk * kAdmScales + 63) / 64), dim3(64), 0, st, b);
-    }
+    });
     PP_HIP(hipGetLastError());
     return PP_OK;
 }

@@ -47,7 +47,6 @@
 // (frame, candidate)'s partials in tile order.  Integers, no atomics: the
 // result does not depend on any order.
 #include <algorithm>
-#include <cstring>
 #include <type_traits>
 
 #include "analysis_dev.hpp"
@@ -232,10 +231,7 @@ extern "C" int pp_frame_sse_band(pp_ctx *ctx, int bitdepth, int w, int h, const 
     if (ndist == 0) return PP_OK;
 
     AlnArgs a{};
-    a.dist = static_cast<const uint8_t *>(dist);
-    a.ref = static_cast<const uint8_t *>(ref);
-    a.dls = dist_linesize; a.dfs = dist_frame_stride;
-    a.rls = ref_linesize; a.rfs = ref_frame_stride;
+    put_luma_pair(a, {ref, ref_linesize, ref_frame_stride, nref}, {dist, dist_linesize, dist_frame_stride, ndist});
     a.rb = (int)g.rb; a.ph = h;
     a.tx = (int)((g.rb + kAlnTileBytes - 1) / kAlnTileBytes);
     a.tiles = a.tx * ((h + kAlnTileRows - 1) / kAlnTileRows);
@@ -248,18 +244,13 @@ extern "C" int pp_frame_sse_band(pp_ctx *ctx, int bitdepth, int w, int h, const 
     if (int e = grow(ctx->aln, sizeof(uint64_t) * (size_t)per * a.tiles * ncand)) return e;
     a.part = static_cast<uint64_t *>(ctx->aln.buf);
 
-    using KFn = void (*)(const AlnArgs);
     const bool aligned = lp.aligned;  // one source off the 16-B grid: both go element by element
-#define PP_ALN_K(ES)                                                                        \
-    (!aligned ? align_kernel<ES, false, true> : ragged ? align_kernel<ES, true, true> \
-                                                       : align_kernel<ES, true, false>)
-    const KFn kern = es == 2 ? PP_ALN_K(2) : PP_ALN_K(1);
-#undef PP_ALN_K
+    const auto kern = es == 2 ? PP_PICK_EDGE(align_kernel, 2, aligned, ragged) : PP_PICK_EDGE(align_kernel, 1, aligned, ragged);
     // `first` travels in the kernel arguments as a frame map does
-    for (int k0 = 0; k0 < ndist; k0 += per) {
+    each_launch(ndist, per, [&](int k0, int nk) {
         AlnArgs b = a;
-        b.nk = std::min(per, ndist - k0);
-        std::memcpy(b.first, first + k0, sizeof(int32_t) * b.nk);
+        b.nk = nk;
+        fill_map(b.first, first, k0, nk);
         b.dist += (int64_t)k0 * a.dfs;
         b.sse = sse + (int64_t)k0 * ncand;
         const int64_t units = (int64_t)b.nk * a.tiles;
@@ -267,7 +258,7 @@ extern "C" int pp_frame_sse_band(pp_ctx *ctx, int bitdepth, int w, int h, const 
         hipLaunchKernelGGL(kern, dim3(groups), dim3(256), 0, st, b);
         const int64_t outs = (int64_t)b.nk * ncand;
         hipLaunchKernelGGL(align_finalize, dim3((unsigned)((outs + 255) / 256)), dim3(256), 0, st, b);
-    }
+    });
     PP_HIP(hipGetLastError());
     return PP_OK;
 }

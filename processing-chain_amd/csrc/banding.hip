@@ -50,7 +50,6 @@
 // integer atomics after its last tile; the result is cleared first.  Integer
 // sums do not depend on any order: two runs give the same bits.
 #include <algorithm>
-#include <cstring>
 
 #include "analysis_dev.hpp"
 #include "analysis_host.hpp"
@@ -312,10 +311,10 @@ extern "C" int pp_banding(pp_ctx *ctx, int bitdepth, int w, int h, const void *s
     a.ws = static_cast<uint16_t *>(ctx->bnd.buf);
     const unsigned ptiles = (unsigned)(((w + kBdMaskCols - 1) / kBdMaskCols) * (int64_t)((h + kBdMaskRows - 1) / kBdMaskRows));
     // launches on one stream run in order, so they share the workspace
-    for (int k0 = 0; k0 < n; k0 += per) {
+    const int rc = each_launch(n, per, [&](int k0, int nk) -> int {
         BdArgs b = a;
-        b.nk = std::min(per, n - k0);
-        for (int k = 0; k < b.nk; ++k) b.idx[k] = index ? index[k0 + k] : k0 + k;
+        b.nk = nk;
+        fill_map(b.idx, index, k0, nk);
         b.hist = hist + (int64_t)k0 * kBdScales * kBdBins;
         PP_HIP(hipMemsetAsync(b.hist, 0, sizeof(uint32_t) * (size_t)b.nk * kBdScales * kBdBins, st));
         if (es == 2) hipLaunchKernelGGL(banding_prep<uint16_t>, dim3(ptiles, b.nk), dim3(256), 0, st, b);
@@ -325,7 +324,9 @@ extern "C" int pp_banding(pp_ctx *ctx, int bitdepth, int w, int h, const void *s
                                dim3(256), 0, st, b, s);
         // far below 2^31 workgroups for planes inside the 2 GiB range and kFrameMap frames
         hipLaunchKernelGGL(banding_contrast, dim3((unsigned)((int64_t)b.nk * a.unit0[kBdScales])), dim3(256), 0, st, b);
-    }
+        return PP_OK;
+    });
+    if (rc) return rc;
     PP_HIP(hipGetLastError());
     return PP_OK;
 }

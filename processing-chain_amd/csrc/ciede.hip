@@ -31,7 +31,6 @@
 // independent of the layout path.
 #include <algorithm>
 #include <cmath>
-#include <cstring>
 
 #include "analysis_dev.hpp"
 #include "analysis_host.hpp"
@@ -281,27 +280,15 @@ extern "C" int pp_ciede(pp_ctx *ctx, int fmt, int w, int h, const pp_frames *ref
     for (double kw : {kL, kC, kH})
         if (!(kw > 0.0) || !std::isfinite(kw)) PP_FAIL(PP_ERR_INVALID, "weights %g, %g, %g (positive and finite)", kL, kC, kH);
     const int bytes = fi.depth > 8 ? 2 : 1;
-    CieArgs a{};
-    bool aligned = true;
-    for (int p = 0; p < 3; ++p) {
-        PlaneGeom g = plane_geom(fmt, w, h, p);
-        const pp_frames *both[2] = {ref, dist};
-        const char *who[2] = {"ref ", "dist "};
-        for (int c = 0; c < 2; ++c) {
-            if (int e = check_plane(both[c], p, g, aligned, 0, who[c])) return e;
-            if (((uintptr_t)both[c]->data[p] | (uint64_t)g.ls | (uint64_t)g.fs) & (bytes - 1))
-                PP_FAIL(PP_ERR_INVALID, "%splane %d: 16-bit samples off the 2-byte grid", who[c], p);
-        }
-        a.ref[p] = static_cast<const uint8_t *>(ref->data[p]);
-        a.dist[p] = static_cast<const uint8_t *>(dist->data[p]);
-        a.rls[p] = ref->linesize[p]; a.rfs[p] = ref->frame_stride[p];
-        a.dls[p] = dist->linesize[p]; a.dfs[p] = dist->frame_stride[p];
-        if (p == 0) { a.w = g.pw; a.h = g.ph; }
-        else { a.cw = g.pw; a.ch = g.ph; }
-    }
+    PairPlanes pl;
+    if (int e = check_pair(pl, fmt, w, h, ref, dist)) return e;
     if (int e = check_frame_map(ref_index, ndist, nref, kRefIndexMap)) return e;
     if (ndist == 0) return PP_OK;
 
+    CieArgs a{};
+    put_pair(a, pl);
+    a.w = pl.g[0].pw; a.h = pl.g[0].ph;
+    a.cw = pl.g[2].pw; a.ch = pl.g[2].ph;
     a.hsub = fi.hsub; a.vsub = fi.vsub;
     const double s = (double)(1 << (fi.depth - 8));
     a.y0 = 16.0 * s; a.yr = 219.0 * s; a.c0 = 128.0 * s; a.cr = 224.0 * s;
@@ -318,18 +305,16 @@ extern "C" int pp_ciede(pp_ctx *ctx, int fmt, int w, int h, const pp_frames *ref
     if (int e = grow(ctx->cie, sizeof(CiePartial) * (size_t)per * a.tiles)) return e;
     a.part = static_cast<CiePartial *>(ctx->cie.buf);
 
-    using KFn = void (*)(const CieArgs);
-    const KFn kern = bytes == 2 ? (aligned ? ciede_kernel<uint16_t, true> : ciede_kernel<uint16_t, false>)
-                                : (aligned ? ciede_kernel<uint8_t, true> : ciede_kernel<uint8_t, false>);
-    for (int k0 = 0; k0 < ndist; k0 += per) {
+    const auto kern = bytes == 2 ? PP_PICK(ciede_kernel, uint16_t, pl.aligned) : PP_PICK(ciede_kernel, uint8_t, pl.aligned);
+    each_launch(ndist, per, [&](int k0, int nk) {
         CieArgs b = a;
-        b.nk = std::min(per, ndist - k0);
-        for (int k = 0; k < b.nk; ++k) b.idx[k] = ref_index ? ref_index[k0 + k] : k0 + k;
+        b.nk = nk;
+        fill_map(b.idx, ref_index, k0, nk);
         for (int p = 0; p < 3; ++p) b.dist[p] += (int64_t)k0 * a.dfs[p];
         b.out = out + 2 * (int64_t)k0;
         hipLaunchKernelGGL(kern, dim3((unsigned)((int64_t)b.nk * a.tiles)), dim3(kCieLanes * kCieWaves), 0, st, b);
         hipLaunchKernelGGL(ciede_finalize, dim3((b.nk + 63) / 64), dim3(64), 0, st, b);
-    }
+    });
     PP_HIP(hipGetLastError());
     return PP_OK;
 }

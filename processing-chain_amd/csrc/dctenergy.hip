@@ -73,7 +73,6 @@
 //            samples has < 2^21 blocks: < 2^56
 // No atomics; integer sums in a fixed order: two runs give the same bits.
 #include <algorithm>
-#include <cstring>
 
 #include "analysis_dev.hpp"
 #include "analysis_host.hpp"
@@ -255,16 +254,9 @@ extern "C" int pp_dct_energy(pp_ctx *ctx, int bitdepth, int w, int h, const void
                              int64_t prev_linesize, uint64_t *out, uint64_t *blocks, void *stream) {
     if (!ctx || !src || !out) PP_FAIL(PP_ERR_INVALID, "null argument");
     LumaPlanes lp;
-    if (int e = luma_open(lp, bitdepth, w, h)) return e;
-    if (n < 0) PP_FAIL(PP_ERR_INVALID, "n %d < 0", n);
-    if (nsrc < 0) PP_FAIL(PP_ERR_INVALID, "nsrc %d < 0", nsrc);
-    if (int e = luma_plane(lp, src, src_linesize, src_frame_stride, "src ")) return e;
-    if (prev)
-        if (int e = luma_plane(lp, prev, prev_linesize, 0, "prev ", 0, true)) return e;
-    if (int e = luma_close(lp)) return e;
-    if (int e = check_frame_map(index, n, nsrc, kIndexMap)) return e;
+    const LumaClip pool{src, src_linesize, src_frame_stride, nsrc}, before{prev, prev_linesize, 0, 1};
+    if (int e = luma_checks(lp, bitdepth, w, h, pool, before, true, index, n, kIndexMap)) return e;
     const int es = lp.es;
-    const bool aligned = lp.aligned;
     if (n == 0) return PP_OK;
 
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -284,29 +276,17 @@ extern "C" int pp_dct_energy(pp_ctx *ctx, int bitdepth, int w, int h, const void
         a.e = static_cast<uint64_t *>(ctx->dct.buf);
         a.dc = reinterpret_cast<int64_t *>(a.e + (size_t)(per + 1) * a.nb);
     }
-    using KFn = void (*)(const DeArgs);
-    const KFn kern = es == 2 ? (aligned ? dct_kernel<uint16_t, true> : dct_kernel<uint16_t, false>)
-                             : (aligned ? dct_kernel<uint8_t, true> : dct_kernel<uint8_t, false>);
-    for (int k0 = 0; k0 < n; k0 += per) {
+    const auto kern = es == 2 ? PP_PICK(dct_kernel, uint16_t, lp.aligned) : PP_PICK(dct_kernel, uint8_t, lp.aligned);
+    each_launch(n, per, [&](int k0, int nk) {
         DeArgs b = a;
-        b.nk = std::min(per, n - k0);
-        for (int k = 0; k < b.nk; ++k) b.idx[k] = index ? index[k0 + k] : k0 + k;
-        const int first_absent = k0 == 0 && !prev;
-        if (k0 > 0) {  // the frame shown before this launch's first
-            b.prev = a.src + (int64_t)(index ? index[k0 - 1] : k0 - 1) * a.fs;
-            b.pls = a.ls;
-        } else if (prev) {
-            b.prev = static_cast<const uint8_t *>(prev);
-            b.pls = prev_linesize;
-        } else {  // none: the first frame stands in, its difference is never reported
-            b.prev = a.src + (int64_t)b.idx[0] * a.fs;
-            b.pls = a.ls;
-        }
+        b.nk = nk;
+        fill_map(b.idx, index, k0, nk);
+        const int first_absent = put_shown_before(b, index, k0, prev, prev_linesize);
         if (a.nb)  // a workgroup per (slot, group): far below 2^31 for planes inside the 2 GiB range and kFrameMap frames
             hipLaunchKernelGGL(kern, dim3((unsigned)((int64_t)(b.nk + 1) * a.groups)), dim3(256), 0, st, b);
         hipLaunchKernelGGL(dct_finalize, dim3(b.nk), dim3(256), 0, st, b.e, b.dc, a.nb, first_absent,
                            out + (int64_t)k0 * 3, blocks ? blocks + (int64_t)k0 * a.nb : nullptr);
-    }
+    });
     PP_HIP(hipGetLastError());
     return PP_OK;
 }

@@ -35,7 +35,6 @@
 // reads uint16_t samples there, so 10-bit planes may sit on the 2-byte grid.
 #include <algorithm>
 #include <cstdlib>
-#include <cstring>
 
 #include "analysis_dev.hpp"
 #include "analysis_host.hpp"
@@ -256,24 +255,16 @@ extern "C" int pp_metrics(pp_ctx *ctx, int fmt, int w, int h, const pp_frames *r
             if (ref_index[k] < 0) PP_FAIL(PP_ERR_INVALID, "ref_index[%d] = %d is negative", k, ref_index[k]);
     const int bytes = fi.depth > 8 ? 2 : 1;
     const int span = kMetWaves * kMetOwnLanes * (kMetLaneBytes / bytes);
+    PairPlanes pl;
+    // the band's halo rows stay inside the buffer range too
+    if (int e = check_pair(pl, fmt, w, h, ref, dist, 4 * (kBandBlocks + 1), "", "", true)) return e;
     MetArgs a{};
     MetFinal f{};
-    bool aligned = true, ragged = false;
+    put_pair(a, pl);
+    bool ragged = false;
     for (int p = 0; p < 3; ++p) {
-        PlaneGeom g = plane_geom(fmt, w, h, p);
-        const int pw = g.pw, ph = g.ph;
-        const pp_frames *both[2] = {ref, dist};
-        for (const pp_frames *fr : both) {
-            // the band's halo rows stay inside the buffer range too
-            if (int e = check_plane(fr, p, g, aligned, 4 * (kBandBlocks + 1), "", false, true)) return e;
-            if (((uintptr_t)fr->data[p] | (uint64_t)g.ls | (uint64_t)g.fs) & (bytes - 1))
-                PP_FAIL(PP_ERR_INVALID, "plane %d: 16-bit samples off the 2-byte grid", p);
-        }
-        ragged |= (g.rb & 15) != 0;
-        a.ref[p] = static_cast<const uint8_t *>(ref->data[p]);
-        a.dist[p] = static_cast<const uint8_t *>(dist->data[p]);
-        a.rls[p] = ref->linesize[p]; a.rfs[p] = ref->frame_stride[p];
-        a.dls[p] = dist->linesize[p]; a.dfs[p] = dist->frame_stride[p];
+        const int pw = pl.g[p].pw, ph = pl.g[p].ph;
+        ragged |= (pl.g[p].rb & 15) != 0;
         a.pw[p] = pw; a.ph[p] = ph;
         a.tiles_x[p] = (pw + span - 1) / span;
         const int bands = (((ph + 3) >> 2) + kBandBlocks - 1) / kBandBlocks;
@@ -291,25 +282,21 @@ extern "C" int pp_metrics(pp_ctx *ctx, int fmt, int w, int h, const pp_frames *r
     if (int e = grow(ctx->met, sizeof(MetPartial) * (size_t)a.tiles * nframes)) return e;
     MetPartial *part = static_cast<MetPartial *>(ctx->met.buf);
 
-    using KFn = void (*)(const MetArgs);
-    const KFn k = bytes == 2 ? (!aligned ? metrics_kernel<uint16_t, false, true>
-                                         : ragged ? metrics_kernel<uint16_t, true, true> : metrics_kernel<uint16_t, true, false>)
-                             : (!aligned ? metrics_kernel<uint8_t, false, true>
-                                         : ragged ? metrics_kernel<uint8_t, true, true> : metrics_kernel<uint8_t, true, false>);
+    const auto k = bytes == 2 ? PP_PICK_EDGE(metrics_kernel, uint16_t, pl.aligned, ragged)
+                              : PP_PICK_EDGE(metrics_kernel, uint8_t, pl.aligned, ragged);
     // identity: one launch over all frames; a map travels in the kernel
     // arguments, kFrameMap dist frames per launch (as pp_stall_compose's)
-    const int per = ref_index ? kFrameMap : nframes;
-    for (int k0 = 0; k0 < nframes; k0 += per) {
+    each_launch(nframes, ref_index ? kFrameMap : nframes, [&](int k0, int nk) {
         MetArgs b = a;
-        b.nk = std::min(per, nframes - k0);
+        b.nk = nk;
         b.identity = ref_index == nullptr;
-        if (ref_index) std::memcpy(b.idx, ref_index + k0, sizeof(int32_t) * b.nk);
+        if (ref_index) fill_map(b.idx, ref_index, k0, nk);  // the identity's launch may pass kFrameMap frames
         for (int p = 0; p < 3; ++p) b.dist[p] += (int64_t)k0 * a.dfs[p];
         b.part = part + (int64_t)k0 * a.tiles;
         const int64_t units = (int64_t)b.nk * a.tiles;
         const int groups = (int)std::min<int64_t>(units, (int64_t)std::max(1, ctx->cus) * 8);
         hipLaunchKernelGGL(k, dim3(groups), dim3(256), 0, st, b);
-    }
+    });
     hipLaunchKernelGGL(metrics_finalize, dim3((nframes * 3 + 63) / 64), dim3(64), 0, st, part, f, nframes, sse, ssim);
     PP_HIP(hipGetLastError());
     return PP_OK;

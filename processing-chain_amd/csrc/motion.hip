@@ -46,7 +46,6 @@
 // per (frame, tile); motion_finalize adds a frame's
 // partials in tile order.  No atomics: two runs give the same bits.
 #include <algorithm>
-#include <cstring>
 
 #include "analysis_dev.hpp"
 #include "analysis_host.hpp"
@@ -217,16 +216,9 @@ extern "C" int pp_motion(pp_ctx *ctx, int bitdepth, int w, int h, const void *sr
                          int64_t prev_linesize, uint64_t *sad, void *stream) {
     if (!ctx || !src || !sad) PP_FAIL(PP_ERR_INVALID, "null argument");
     LumaPlanes lp;
-    if (int e = luma_open(lp, bitdepth, w, h)) return e;
-    if (n < 0) PP_FAIL(PP_ERR_INVALID, "n %d < 0", n);
-    if (nsrc < 0) PP_FAIL(PP_ERR_INVALID, "nsrc %d < 0", nsrc);
-    if (int e = luma_plane(lp, src, src_linesize, src_frame_stride, "src ")) return e;
-    if (prev)
-        if (int e = luma_plane(lp, prev, prev_linesize, 0, "prev ", 0, true)) return e;
-    if (int e = luma_close(lp)) return e;
-    if (int e = check_frame_map(index, n, nsrc, kIndexMap)) return e;
+    const LumaClip pool{src, src_linesize, src_frame_stride, nsrc}, before{prev, prev_linesize, 0, 1};
+    if (int e = luma_checks(lp, bitdepth, w, h, pool, before, true, index, n, kIndexMap)) return e;
     const int es = lp.es;
-    const bool aligned = lp.aligned;
     if (n == 0) return PP_OK;
 
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -244,24 +236,12 @@ extern "C" int pp_motion(pp_ctx *ctx, int bitdepth, int w, int h, const void *sr
         if (int e = grow(ctx->mot, sizeof(uint64_t) * (size_t)per * a.tiles)) return e;
         a.part = static_cast<uint64_t *>(ctx->mot.buf);
     }
-    using KFn = void (*)(const MoArgs);
-    const KFn kern = es == 2 ? (aligned ? motion_kernel<uint16_t, true> : motion_kernel<uint16_t, false>)
-                             : (aligned ? motion_kernel<uint8_t, true> : motion_kernel<uint8_t, false>);
-    for (int k0 = 0; k0 < n; k0 += per) {
+    const auto kern = es == 2 ? PP_PICK(motion_kernel, uint16_t, lp.aligned) : PP_PICK(motion_kernel, uint8_t, lp.aligned);
+    each_launch(n, per, [&](int k0, int nk) {
         MoArgs b = a;
-        b.nk = std::min(per, n - k0);
-        for (int k = 0; k < b.nk; ++k) b.idx[k] = index ? index[k0 + k] : k0 + k;
-        b.first_absent = k0 == 0 && !prev;
-        if (k0 > 0) {  // the frame shown before this launch's first
-            b.prev = a.src + (int64_t)(index ? index[k0 - 1] : k0 - 1) * a.fs;
-            b.pls = a.ls;
-        } else if (prev) {
-            b.prev = static_cast<const uint8_t *>(prev);
-            b.pls = prev_linesize;
-        } else {  // none: the first frame stands in, its sum is never reported
-            b.prev = a.src + (int64_t)b.idx[0] * a.fs;
-            b.pls = a.ls;
-        }
+        b.nk = nk;
+        fill_map(b.idx, index, k0, nk);
+        b.first_absent = put_shown_before(b, index, k0, prev, prev_linesize);
         b.sad = sad + k0;
         if (!none) {
             const int segs = (b.nk + kMoSeg - 1) / kMoSeg;
@@ -270,7 +250,7 @@ extern "C" int pp_motion(pp_ctx *ctx, int bitdepth, int w, int h, const void *sr
         }
         hipLaunchKernelGGL(motion_finalize, dim3((b.nk + 63) / 64), dim3(64), 0, st, b.part, b.nk, a.tiles,
                            b.first_absent, none ? 1 : 0, b.sad);
-    }
+    });
     PP_HIP(hipGetLastError());
     return PP_OK;
 }

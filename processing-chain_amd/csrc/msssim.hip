@@ -34,7 +34,6 @@
 // give the same bits.
 #include <algorithm>
 #include <cmath>
-#include <cstring>
 
 #include "analysis_dev.hpp"
 #include "analysis_host.hpp"
@@ -196,22 +195,15 @@ extern "C" int pp_ms_ssim(pp_ctx *ctx, int bitdepth, int w, int h, const void *r
                           int64_t ref_frame_stride, int nref, const void *dist, int64_t dist_linesize,
                           int64_t dist_frame_stride, int ndist, const int32_t *ref_index, double *out, void *stream) {
     if (!ctx || !ref || !dist || !out) PP_FAIL(PP_ERR_INVALID, "null argument");
+    const LumaClip r{ref, ref_linesize, ref_frame_stride, nref}, d{dist, dist_linesize, dist_frame_stride, ndist};
     LumaPlanes lp;
-    if (int e = luma_open(lp, bitdepth, w, h)) return e;
-    if (ndist < 0) PP_FAIL(PP_ERR_INVALID, "ndist %d < 0", ndist);
-    if (nref < 0) PP_FAIL(PP_ERR_INVALID, "nref %d < 0", nref);
-    if (int e = luma_plane(lp, ref, ref_linesize, ref_frame_stride, "ref ")) return e;
-    if (int e = luma_plane(lp, dist, dist_linesize, dist_frame_stride, "dist ")) return e;
-    if (int e = luma_close(lp)) return e;  // one element-wise path: lp.aligned is not looked at
-    if (int e = check_frame_map(ref_index, ndist, nref, kRefIndexMap)) return e;
+    // one element-wise path: lp.aligned is not looked at
+    if (int e = luma_checks(lp, bitdepth, w, h, r, d, false, ref_index, ndist, kRefIndexMap)) return e;
     const int es = lp.es;
     if (ndist == 0) return PP_OK;
 
     MsArgs a{};
-    a.ref = static_cast<const uint8_t *>(ref);
-    a.dist = static_cast<const uint8_t *>(dist);
-    a.rls = ref_linesize; a.rfs = ref_frame_stride;
-    a.dls = dist_linesize; a.dfs = dist_frame_stride;
+    put_luma_pair(a, r, d);
     for (int s = 0; s < kMsScales; ++s) {
         a.ws[s] = w >> s; a.hs[s] = h >> s;
         const bool any = a.ws[s] >= kMsTaps && a.hs[s] >= kMsTaps;
@@ -242,10 +234,10 @@ extern "C" int pp_ms_ssim(pp_ctx *ctx, int bitdepth, int w, int h, const void *r
 
     const int cus = std::max(1, ctx->cus);
     auto blocks = [&](int64_t n) { return dim3((unsigned)std::min<int64_t>((n + 255) / 256, (int64_t)cus * 64)); };
-    for (int k0 = 0; k0 < ndist; k0 += per) {
+    each_launch(ndist, per, [&](int k0, int nk) {
         MsArgs b = a;
-        b.nk = std::min(per, ndist - k0);
-        for (int k = 0; k < b.nk; ++k) b.idx[k] = ref_index ? ref_index[k0 + k] : k0 + k;
+        b.nk = nk;
+        fill_map(b.idx, ref_index, k0, nk);
         b.dist += (int64_t)k0 * a.dfs;
         b.out = out + (int64_t)k0 * kMsScales * 2;
         for (int s = 1; s < kMsScales; ++s) {
@@ -262,7 +254,7 @@ extern "C" int pp_ms_ssim(pp_ctx *ctx, int bitdepth, int w, int h, const void *r
             else hipLaunchKernelGGL(msssim_kernel<uint8_t>, grid, dim3(256), 0, st, b);
         }
         hipLaunchKernelGGL(msssim_finalize, dim3((b.nk * kMsScales + 63) / 64), dim3(64), 0, st, b);
-    }
+    });
     PP_HIP(hipGetLastError());
     return PP_OK;
 }

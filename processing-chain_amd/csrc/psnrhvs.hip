@@ -37,7 +37,6 @@
 // Arithmetic: fp64 throughout in the spec's order, contraction off; the fused
 // multiply-adds of the transform are the spec's.
 #include <algorithm>
-#include <cstring>
 
 #include "analysis_dev.hpp"
 #include "analysis_host.hpp"
@@ -293,21 +292,15 @@ extern "C" int pp_psnr_hvs(pp_ctx *ctx, int fmt, int w, int h, const pp_frames *
     if (nref < 0) PP_FAIL(PP_ERR_INVALID, "nref %d < 0", nref);
     if (step != 7 && step != 8) PP_FAIL(PP_ERR_INVALID, "step %d (7 or 8)", step);
     const int bytes = fi.depth > 8 ? 2 : 1;
+    PairPlanes pl;
+    if (int e = check_pair(pl, fmt, w, h, ref, dist)) return e;
+    if (int e = check_frame_map(ref_index, ndist, nref, kRefIndexMap)) return e;
+    if (ndist == 0) return PP_OK;
+
     HvsArgs a{};
-    bool aligned = true;
+    put_pair(a, pl);
     for (int p = 0; p < 3; ++p) {
-        PlaneGeom g = plane_geom(fmt, w, h, p);
-        const pp_frames *both[2] = {ref, dist};
-        const char *who[2] = {"ref ", "dist "};
-        for (int c = 0; c < 2; ++c) {
-            if (int e = check_plane(both[c], p, g, aligned, 0, who[c])) return e;
-            if (((uintptr_t)both[c]->data[p] | (uint64_t)g.ls | (uint64_t)g.fs) & (bytes - 1))
-                PP_FAIL(PP_ERR_INVALID, "%splane %d: 16-bit samples off the 2-byte grid", who[c], p);
-        }
-        a.ref[p] = static_cast<const uint8_t *>(ref->data[p]);
-        a.dist[p] = static_cast<const uint8_t *>(dist->data[p]);
-        a.rls[p] = ref->linesize[p]; a.rfs[p] = ref->frame_stride[p];
-        a.dls[p] = dist->linesize[p]; a.dfs[p] = dist->frame_stride[p];
+        const PlaneGeom &g = pl.g[p];
         a.ph[p] = g.ph; a.rb[p] = (int)g.rb;
         // blocks of an axis of n samples: origins i step with i step + 8 <= n
         const int nbx = g.pw < kHvsN ? 0 : (g.pw - kHvsN) / step + 1;
@@ -317,8 +310,6 @@ extern "C" int pp_psnr_hvs(pp_ctx *ctx, int fmt, int w, int h, const pp_frames *
         a.tile0[p] = a.tiles;
         a.tiles += nbx ? a.gx[p] * nby : 0;
     }
-    if (int e = check_frame_map(ref_index, ndist, nref, kRefIndexMap)) return e;
-    if (ndist == 0) return PP_OK;
     a.step = step;
 
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -328,19 +319,17 @@ extern "C" int pp_psnr_hvs(pp_ctx *ctx, int fmt, int w, int h, const pp_frames *
     if (int e = grow(ctx->hvs, sizeof(double2) * (size_t)per * a.tiles)) return e;
     a.part = static_cast<double2 *>(ctx->hvs.buf);
 
-    using KFn = void (*)(const HvsArgs);
-    const KFn kern = bytes == 2 ? (aligned ? hvs_kernel<uint16_t, true> : hvs_kernel<uint16_t, false>)
-                                : (aligned ? hvs_kernel<uint8_t, true> : hvs_kernel<uint8_t, false>);
-    for (int k0 = 0; k0 < ndist; k0 += per) {
+    const auto kern = bytes == 2 ? PP_PICK(hvs_kernel, uint16_t, pl.aligned) : PP_PICK(hvs_kernel, uint8_t, pl.aligned);
+    each_launch(ndist, per, [&](int k0, int nk) {
         HvsArgs b = a;
-        b.nk = std::min(per, ndist - k0);
-        for (int k = 0; k < b.nk; ++k) b.idx[k] = ref_index ? ref_index[k0 + k] : k0 + k;
+        b.nk = nk;
+        fill_map(b.idx, ref_index, k0, nk);
         for (int p = 0; p < 3; ++p) b.dist[p] += (int64_t)k0 * a.dfs[p];
         b.out = out + 6 * (int64_t)k0;
         if (a.tiles)  // a frame under 8 samples in a direction has no unit
             hipLaunchKernelGGL(kern, dim3((unsigned)((int64_t)b.nk * a.tiles)), dim3(64 * kHvsWaves), 0, st, b);
         hipLaunchKernelGGL(hvs_finalize, dim3(3 * b.nk), dim3(64), 0, st, b);
-    }
+    });
     PP_HIP(hipGetLastError());
     return PP_OK;
 }

@@ -464,9 +464,12 @@ def _ref_dist(who, entry, ref_batch, dist_batch, ref_index, tail, stream):
     return out
 
 
-def _sequence(s, index, tail, dtype):
-    """The (sequence, index) family, for the luma ``s``: (index as int32 or
-    None, the result [n, *tail] to fill, n the shown frames)."""
+def _sequence(who, batch_or_luma, bitdepth, index, tail, dtype):
+    """The (sequence, index) family, for the operation ``who``: (the luma, its
+    own bit depth, the one to pass, index as int32 or None, the result
+    [n, *tail] to fill, n the shown frames)."""
+    s, sd = _luma(batch_or_luma, who)
+    d = sd if bitdepth is None else int(bitdepth)
     idx = None
     n = s.shape[0]
     if index is not None:
@@ -475,7 +478,17 @@ def _sequence(s, index, tail, dtype):
     out = torch.empty((n,) + tail, dtype=dtype, device=s.device)
     if n and s.shape[0] == 0:
         raise ValueError("index names frames of an empty batch")
-    return idx, out
+    return s, sd, d, idx, out
+
+
+def _sequence_call(entry, s, d, idx, out, args, stream):
+    """Fills ``out`` through the library's ``entry``; ``args`` stand between n and the stream."""
+    nsrc, h, w = s.shape
+    es = s.element_size()
+    ctx = context(s.device.index)
+    check(getattr(lib(), entry)(ctx.handle, d, w, h, ctypes.c_void_p(s.data_ptr()), s.stride(1) * es, s.stride(0) * es,
+                                nsrc, None if idx is None else idx.ctypes.data, out.shape[0], *args, _stream(s, stream)))
+    return out
 
 
 def sse_band(ref_batch, dist_batch, first, ncand, stream=None):
@@ -545,6 +558,27 @@ def adm(ref_batch, dist_batch, ref_index=None, stream=None):
     return _ref_dist("adm", "pp_adm", ref_batch, dist_batch, ref_index, (4, 6), stream)
 
 
+def _planar_pair(who, entry, f, ref, dist, ref_index, options, tail, stream):
+    """The planar (ref, dist, ref_index) family: the operation ``who`` on
+    FrameBatches of the format ``f`` calls the library's ``entry`` and returns
+    its float64 [ndist, *tail] on the device.  ``options()`` gives the
+    arguments between ndist and the result; an empty batch does not ask."""
+    if f.packed:
+        raise ValueError("%s takes planar frames: unpack %s first (ops.unpack)" % (who, f.name))
+    _same_frames(ref, dist, f)
+    n = dist.n
+    idx = _ref_index(ref_index, n)
+    out = torch.empty((n,) + tail, dtype=torch.float64, device=dist.device)
+    if n == 0:  # an empty batch has no plane pointers to pass
+        return out
+    ctx = context(dist.device.index)
+    r, d = (ref if ref.n else dist).frames_struct(), dist.frames_struct()  # an empty reference: the call rejects the map
+    check(getattr(lib(), entry)(ctx.handle, f.id, dist.w, dist.h, ctypes.byref(r), ctypes.byref(d),
+                                None if idx is None else idx.ctypes.data, ref.n, n, *options(),
+                                ctypes.c_void_p(out.data_ptr()), _stream(dist.planes[0], stream)))
+    return out
+
+
 def ciede(ref, dist, fmt=None, ref_index=None, weights=(1, 1, 1), stream=None):
     """Per-frame CIEDE2000 sums of ``dist`` against ``ref`` (spec PP-CIEDE-1,
     pp_ciede): two FrameBatches of one planar format and size, any pitches.
@@ -555,21 +589,8 @@ def ciede(ref, dist, fmt=None, ref_index=None, weights=(1, 1, 1), stream=None):
     the sum of dE00 over the w h luma positions and out[k, 1] the largest.
     pixpath.ciede.pool turns it into delta_e, delta_e_max and ciede2000."""
     f = dist.fmt if fmt is None else formats.fmt(fmt)
-    if f.packed:
-        raise ValueError("ciede takes planar frames: unpack %s first (ops.unpack)" % f.name)
-    _same_frames(ref, dist, f)
-    n = dist.n
-    idx = _ref_index(ref_index, n)
     kL, kC, kH = (float(v) for v in weights)
-    out = torch.empty((n, 2), dtype=torch.float64, device=dist.device)
-    if n == 0:  # an empty batch has no plane pointers to pass
-        return out
-    ctx = context(dist.device.index)
-    r, d = (ref if ref.n else dist).frames_struct(), dist.frames_struct()  # an empty reference: the call rejects the map
-    check(lib().pp_ciede(ctx.handle, f.id, dist.w, dist.h, ctypes.byref(r), ctypes.byref(d),
-                         None if idx is None else idx.ctypes.data, ref.n, n, kL, kC, kH,
-                         ctypes.c_void_p(out.data_ptr()), _stream(dist.planes[0], stream)))
-    return out
+    return _planar_pair("ciede", "pp_ciede", f, ref, dist, ref_index, lambda: (kL, kC, kH), (2,), stream)
 
 
 def psnr_hvs(ref, dist, ref_index=None, step=8, stream=None):
@@ -581,21 +602,7 @@ def psnr_hvs(ref, dist, ref_index=None, step=8, stream=None):
     the current stream: out[k, p, 0] = S_hvs and out[k, p, 1] = S_hvsm of plane
     p over its 8 x 8 blocks, 0.0 for a plane with no block.
     pixpath.psnrhvs.pool turns it into the MSE and PSNR values."""
-    f = dist.fmt
-    if f.packed:
-        raise ValueError("psnr_hvs takes planar frames: unpack %s first (ops.unpack)" % f.name)
-    _same_frames(ref, dist, f)
-    n = dist.n
-    idx = _ref_index(ref_index, n)
-    out = torch.empty((n, 3, 2), dtype=torch.float64, device=dist.device)
-    if n == 0:  # an empty batch has no plane pointers to pass
-        return out
-    ctx = context(dist.device.index)
-    r, d = (ref if ref.n else dist).frames_struct(), dist.frames_struct()  # an empty reference: the call rejects the map
-    check(lib().pp_psnr_hvs(ctx.handle, f.id, dist.w, dist.h, ctypes.byref(r), ctypes.byref(d),
-                            None if idx is None else idx.ctypes.data, ref.n, n, int(step),
-                            ctypes.c_void_p(out.data_ptr()), _stream(dist.planes[0], stream)))
-    return out
+    return _planar_pair("psnr_hvs", "pp_psnr_hvs", dist.fmt, ref, dist, ref_index, lambda: [int(step)], (3, 2), stream)
 
 
 def motion(batch_or_luma, bitdepth=None, index=None, prev=None, stream=None):
@@ -609,20 +616,11 @@ def motion(batch_or_luma, bitdepth=None, index=None, prev=None, stream=None):
     sad[k] = sum |B(frame k) - B(frame k - 1)| over the plane, exact; sad[0]
     without ``prev``, and every entry of a plane under 3 x 3, is 2^64 - 1 =
     absent.  pixpath.motion.pool turns it into motion and motion2."""
-    s, sd = _luma(batch_or_luma, "motion")
-    d = sd if bitdepth is None else int(bitdepth)
-    idx, out = _sequence(s, index, (), torch.uint64)
-    n = out.shape[0]
-    if n == 0:  # an empty sequence has no data pointer to pass
+    s, sd, d, idx, out = _sequence("motion", batch_or_luma, bitdepth, index, (), torch.uint64)
+    if out.shape[0] == 0:  # an empty sequence has no data pointer to pass
         return out
-    nsrc, h, w = s.shape
-    es = s.element_size()
     pp, pls = _prev_plane(prev, s, sd, "motion")
-    ctx = context(s.device.index)
-    check(lib().pp_motion(ctx.handle, d, w, h, ctypes.c_void_p(s.data_ptr()), s.stride(1) * es, s.stride(0) * es, nsrc,
-                          None if idx is None else idx.ctypes.data, n, pp, pls, ctypes.c_void_p(out.data_ptr()),
-                          _stream(s, stream)))
-    return out
+    return _sequence_call("pp_motion", s, d, idx, out, (pp, pls, ctypes.c_void_p(out.data_ptr())), stream)
 
 
 def banding(batch_or_luma, bitdepth=None, index=None, window=None, tvi=None, stream=None):
@@ -638,25 +636,18 @@ def banding(batch_or_luma, bitdepth=None, index=None, window=None, tvi=None, str
     frame k with contrast value q.  pixpath.banding.pool turns it into the
     banding index."""
     from . import banding as _banding
-    s, sd = _luma(batch_or_luma, "banding")
-    d = sd if bitdepth is None else int(bitdepth)
-    idx, out = _sequence(s, index, (_banding.SCALES, _banding.BINS), torch.uint32)
-    n = out.shape[0]
-    if n == 0:  # an empty sequence has no data pointer to pass
+    s, _, d, idx, out = _sequence("banding", batch_or_luma, bitdepth, index, (_banding.SCALES, _banding.BINS), torch.uint32)
+    if out.shape[0] == 0:  # an empty sequence has no data pointer to pass
         return out
-    nsrc, h, w = s.shape
+    h, w = s.shape[1:]
     win = _banding.default_window(w, h) if window is None else int(window)
     tv = None
     if tvi is not None:
         tv = np.ascontiguousarray(tvi, dtype=np.uint16).reshape(-1)
         if tv.shape != (4,):
             raise ValueError("tvi needs four entries")
-    es = s.element_size()
-    ctx = context(s.device.index)
-    check(lib().pp_banding(ctx.handle, d, w, h, ctypes.c_void_p(s.data_ptr()), s.stride(1) * es, s.stride(0) * es, nsrc,
-                           None if idx is None else idx.ctypes.data, n, win, None if tv is None else tv.ctypes.data,
-                           ctypes.c_void_p(out.data_ptr()), _stream(s, stream)))
-    return out
+    return _sequence_call("pp_banding", s, d, idx, out,
+                          (win, None if tv is None else tv.ctypes.data, ctypes.c_void_p(out.data_ptr())), stream)
 
 
 def dct_energy(batch_or_luma, bitdepth=None, index=None, prev=None, blocks=False, stream=None):
@@ -670,23 +661,16 @@ def dct_energy(batch_or_luma, bitdepth=None, index=None, prev=None, blocks=False
     blocks' energies, the spatial complexity map.  pixpath.dctenergy.pool
     turns the sums into E, h and L."""
     from . import dctenergy as _dct
-    s, sd = _luma(batch_or_luma, "dct_energy")
-    d = sd if bitdepth is None else int(bitdepth)
-    idx, out = _sequence(s, index, (3,), torch.uint64)
+    s, sd, d, idx, out = _sequence("dct_energy", batch_or_luma, bitdepth, index, (3,), torch.uint64)
     n = out.shape[0]
-    nsrc, h, w = s.shape
-    bx, by = _dct.geometry(w, h)
+    bx, by = _dct.geometry(s.shape[2], s.shape[1])
     bl = torch.empty((n, by, bx), dtype=torch.uint64, device=s.device) if blocks else None
     if n == 0:  # an empty sequence has no data pointer to pass
         return (out, bl) if blocks else out
-    es = s.element_size()
     pp, pls = _prev_plane(prev, s, sd, "dct_energy")
-    ctx = context(s.device.index)
     # a map without a block has no data pointer: NULL, nothing is written
     bp = ctypes.c_void_p(bl.data_ptr()) if blocks and bx * by else None
-    check(lib().pp_dct_energy(ctx.handle, d, w, h, ctypes.c_void_p(s.data_ptr()), s.stride(1) * es, s.stride(0) * es,
-                              nsrc, None if idx is None else idx.ctypes.data, n, pp, pls,
-                              ctypes.c_void_p(out.data_ptr()), bp, _stream(s, stream)))
+    _sequence_call("pp_dct_energy", s, d, idx, out, (pp, pls, ctypes.c_void_p(out.data_ptr()), bp), stream)
     return (out, bl) if blocks else out
 
 

@@ -27,17 +27,15 @@ be wrong: the minimum sizes, odd sizes, and per scale one coefficient below,
 at and above the seams of the tiling (a wave's first 63 columns, a tile's 254
 columns, a band's 32 rows), all with poisoned pitch padding.  Every call writes
 into a larger, sentinel-filled output and must change [ndist][4][6] alone."""
-import ctypes
 
 import numpy as np
 import pytest
 
 import adm_ref as R
-from test_gpu_vif import _make
+from gpu_calls import SENTINEL, call_pair, make as _make
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0x5A5A5A5A5A5A5A5A
 CPU_SPREAD = 2.08e-13
 MEASURED = 5.41e-12
 REL = 100 * MEASURED
@@ -83,27 +81,10 @@ def compare(got, want, w, h, peak, label=""):
     return worst
 
 
-def _call(gpu, depth, w, h, ref, dist, idx=None, nd=None, nr=None, rls=None, dls=None, null=()):
+def _call(gpu, depth, w, h, ref, dist, *args, **kw):
     """pp_adm itself on a sentinel-filled output of two frames more than it
     needs; returns (rc, out [nd, 4, 6] float64, untouched: everything else kept the sentinel)."""
-    import torch
-    from pixpath import _native, ops
-    L = _native.lib()
-    nd = dist.shape[0] if nd is None else nd
-    nr = ref.shape[0] if nr is None else nr
-    es = dist.element_size()
-    out = torch.full((max(nd, 0) + 2, 4, 6), SENTINEL, dtype=torch.int64, device=gpu)
-    ix = None if idx is None else np.ascontiguousarray(idx, dtype=np.int32)
-    ptr = lambda name, v: None if name in null else ctypes.c_void_p(v)
-    rc = L.pp_adm(None if "ctx" in null else ops.context(gpu.index).handle, depth, w, h,
-                  ptr("ref", ref.data_ptr()), ref.stride(1) * es if rls is None else rls, ref.stride(0) * es, nr,
-                  ptr("dist", dist.data_ptr()), dist.stride(1) * es if dls is None else dls, dist.stride(0) * es,
-                  nd, None if ix is None else ix.ctypes.data, ptr("out", out.data_ptr()),
-                  ctypes.c_void_p(torch.cuda.current_stream(gpu).cuda_stream))
-    torch.cuda.synchronize(gpu)
-    raw = out.cpu().numpy()
-    n = max(nd, 0) if rc == 0 else 0
-    return rc, raw[:n].view(np.float64), bool((raw[n:] == SENTINEL).all())
+    return call_pair(gpu, "pp_adm", (4, 6), depth, w, h, ref, dist, *args, **kw)
 
 
 def _check(gpu, depth, a, b, idx=None, rl="std", dl="std", label=""):

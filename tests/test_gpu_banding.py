@@ -4,24 +4,22 @@ np.array_equal, no tolerance.
 
 Every call of pp_banding itself writes into a sentinel-filled output two frames
 longer than it needs and must change [n][5][1024] alone; planes carry poisoned
-pitch padding (test_gpu_vif._make).  The content is banding_ref.content, half
+pitch padding (gpu_calls.make).  The content is banding_ref.content, half
 banded and half noisy (test_banding_host checks that it exercises the mask, the
 window and several bins).  The shapes are the smallest at which the kernels can
 still be wrong: 1 x 1, a row, a column, the mask's 7 x 7, a window larger than
 the plane, and widths and heights one below, at and one above the tiles of the
 mask kernel (32 rows x 64 columns) and of the contrast kernel (32 x 32), and
 two tiles and a sample, which is also more than one chunk of tiles."""
-import ctypes
 
 import numpy as np
 import pytest
 
 import banding_ref as R
-from test_gpu_vif import _make
+from gpu_calls import call_sequence, make as _make, untouched
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0x5A5A5A5A
 _REF = {}
 
 
@@ -45,24 +43,10 @@ def _want(a, depth, window, idx=None, tvi=None):
 def _call(gpu, depth, w, h, src, window, idx=None, n=None, nsrc=None, tvi=None, sls=None, null=()):
     """pp_banding itself on a sentinel-filled output of two frames more than it
     needs; returns (rc, hist [n, 5, 1024] uint32, untouched: everything else kept the sentinel)."""
-    import torch
-    from pixpath import _native, ops
-    L = _native.lib()
-    nsrc = src.shape[0] if nsrc is None else nsrc
-    ix = None if idx is None else np.ascontiguousarray(idx, dtype=np.int32)
     tv = None if tvi is None else np.ascontiguousarray(tvi, dtype=np.uint16)
-    n = (nsrc if ix is None else len(ix)) if n is None else n
-    es = src.element_size()
-    out = torch.full((max(n, 0) + 2, 5, 1024), SENTINEL, dtype=torch.int32, device=gpu)
-    ptr = lambda name, v: None if name in null else ctypes.c_void_p(v)
-    rc = L.pp_banding(None if "ctx" in null else ops.context(gpu.index).handle, depth, w, h,
-                      ptr("src", src.data_ptr()), src.stride(1) * es if sls is None else sls, src.stride(0) * es, nsrc,
-                      None if ix is None else ix.ctypes.data, n, window, None if tv is None else tv.ctypes.data,
-                      ptr("hist", out.data_ptr()), ctypes.c_void_p(torch.cuda.current_stream(gpu).cuda_stream))
-    torch.cuda.synchronize(gpu)
-    raw = out.cpu().numpy().view(np.uint32)
-    k = max(n, 0) if rc == 0 else 0
-    return rc, raw[:k].copy(), bool((raw[k:] == SENTINEL).all())
+    rc, k, (raw,) = call_sequence(gpu, "pp_banding", depth, w, h, src, (window, None if tv is None else tv.ctypes.data),
+                                  [("hist", (5, 1024), "int32")], idx, n, nsrc, sls, null)
+    return rc, raw[:k].copy(), untouched(raw, k)
 
 
 def _check(gpu, depth, a, window, idx=None, tvi=None, layout="std", label=""):

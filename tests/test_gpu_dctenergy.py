@@ -4,23 +4,21 @@ tolerance.
 
 Every call of pp_dct_energy itself writes into sentinel-filled outputs two
 frames longer than it needs and must change [n] alone; planes carry poisoned
-pitch padding (test_gpu_vif._make).  The shapes are the smallest at which the
+pitch padding (gpu_calls.make).  The shapes are the smallest at which the
 kernel can still be wrong: 31 x 40 and 40 x 31 (no block), 32, 33, 63, 64 and
 65 in each direction, block counts one below, at and one above each seam it has
 (a wave's 2 blocks, a workgroup's 8, the 256 lanes of the finalize kernel),
 257 shown frames for the launch seam, both depths, on and off the 16-B grid,
 with and without `prev`."""
-import ctypes
 
 import numpy as np
 import pytest
 
 import dctenergy_ref as R
-from test_gpu_vif import _make
+from gpu_calls import call_sequence, make as _make, prev_args, untouched
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0x5A5A5A5A5A5A5A5A
 ABSENT = (1 << 64) - 1
 _REF = {}
 
@@ -47,35 +45,16 @@ def _call(gpu, depth, w, h, src, idx=None, n=None, nsrc=None, prev=None, sls=Non
     """pp_dct_energy itself on sentinel-filled outputs of two frames more than
     it needs; returns (rc, out as n rows of Python ints, blocks as n [by][bx]
     lists or None, untouched: everything else kept the sentinel)."""
-    import torch
-    from pixpath import _native, ops
-    L = _native.lib()
-    nsrc = src.shape[0] if nsrc is None else nsrc
-    ix = None if idx is None else np.ascontiguousarray(idx, dtype=np.int32)
-    n = (nsrc if ix is None else len(ix)) if n is None else n
-    es = src.element_size()
     bx, by = max(w, 0) // 32, max(h, 0) // 32
     nb = bx * by
-    out = torch.full((max(n, 0) + 2, 3), SENTINEL, dtype=torch.int64, device=gpu)
-    bl = torch.full((max(n, 0) + 2, max(nb, 1)), SENTINEL, dtype=torch.int64, device=gpu)
-    ptr = lambda name, v: None if name in null else ctypes.c_void_p(v)
-    rc = L.pp_dct_energy(None if "ctx" in null else ops.context(gpu.index).handle, depth, w, h,
-                         ptr("src", src.data_ptr()), src.stride(1) * es if sls is None else sls, src.stride(0) * es, nsrc,
-                         None if ix is None else ix.ctypes.data, n,
-                         None if prev is None else ctypes.c_void_p(prev.data_ptr()),
-                         0 if prev is None else (prev.stride(1) * es if pls is None else pls),
-                         ptr("out", out.data_ptr()), ctypes.c_void_p(bl.data_ptr()) if blocks else None,
-                         ctypes.c_void_p(torch.cuda.current_stream(gpu).cuda_stream))
-    torch.cuda.synchronize(gpu)
-    raw = out.cpu().numpy().view(np.uint64)
-    rawb = bl.cpu().numpy().view(np.uint64)
-    k = max(n, 0) if rc == 0 else 0
+    rc, k, (raw, rawb) = call_sequence(gpu, "pp_dct_energy", depth, w, h, src, prev_args(prev, pls),
+                                       [("out", (3,), "int64"), ("blocks", (max(nb, 1),), "int64")], idx, n, nsrc, sls,
+                                       tuple(null) + (() if blocks else ("blocks",)))
     kb = k if (blocks and nb) else 0
-    untouched = bool((raw[k:] == SENTINEL).all()) and bool((rawb[kb:] == SENTINEL).all())
     got_b = None
     if blocks:
         got_b = [[[int(v) for v in rawb[f, j * bx:(j + 1) * bx]] for j in range(by)] if nb else [] for f in range(k)]
-    return rc, [[int(v) for v in row] for row in raw[:k]], got_b, untouched
+    return rc, [[int(v) for v in row] for row in raw[:k]], got_b, untouched(raw, k) and untouched(rawb, kb)
 
 
 def _check(gpu, depth, a, idx=None, prev=None, layout="std", player="std", label=""):

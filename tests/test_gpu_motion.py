@@ -4,23 +4,21 @@ np.array_equal, no tolerance.
 
 Every call of pp_motion itself writes into a sentinel-filled output two entries
 longer than it needs and must change [n] alone; planes carry poisoned pitch
-padding (test_gpu_vif._make).  The shapes are the smallest at which the kernel
+padding (gpu_calls.make).  The shapes are the smallest at which the kernel
 can still be wrong: 3 x 3, 3 x 40, 40 x 3, and widths and heights one below, at
 and one above each seam it has (a lane's piece of 16 B, a tile's 62 pieces, a
 wave's 64 pieces, a wave's 16 rows, a tile's 64 rows), sequences one below, at
 and one above the segment of 4 shown frames, both depths, on and off the 16-B
 grid, with and without `prev`."""
-import ctypes
 
 import numpy as np
 import pytest
 
 import motion_ref as R
-from test_gpu_vif import _make
+from gpu_calls import call_sequence, make as _make, prev_args, untouched
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0x5A5A5A5A5A5A5A5A
 ABSENT = (1 << 64) - 1
 _REF = {}
 
@@ -45,25 +43,9 @@ def _want(a, depth, idx=None, prev=None):
 def _call(gpu, depth, w, h, src, idx=None, n=None, nsrc=None, prev=None, sls=None, pls=None, null=()):
     """pp_motion itself on a sentinel-filled output of two entries more than it
     needs; returns (rc, sad as a list of Python ints, untouched: everything else kept the sentinel)."""
-    import torch
-    from pixpath import _native, ops
-    L = _native.lib()
-    nsrc = src.shape[0] if nsrc is None else nsrc
-    ix = None if idx is None else np.ascontiguousarray(idx, dtype=np.int32)
-    n = (nsrc if ix is None else len(ix)) if n is None else n
-    es = src.element_size()
-    out = torch.full((max(n, 0) + 2,), SENTINEL, dtype=torch.int64, device=gpu)
-    ptr = lambda name, v: None if name in null else ctypes.c_void_p(v)
-    rc = L.pp_motion(None if "ctx" in null else ops.context(gpu.index).handle, depth, w, h,
-                     ptr("src", src.data_ptr()), src.stride(1) * es if sls is None else sls, src.stride(0) * es, nsrc,
-                     None if ix is None else ix.ctypes.data, n,
-                     None if prev is None else ctypes.c_void_p(prev.data_ptr()),
-                     0 if prev is None else (prev.stride(1) * es if pls is None else pls),
-                     ptr("sad", out.data_ptr()), ctypes.c_void_p(torch.cuda.current_stream(gpu).cuda_stream))
-    torch.cuda.synchronize(gpu)
-    raw = out.cpu().numpy().view(np.uint64)
-    k = max(n, 0) if rc == 0 else 0
-    return rc, [int(v) for v in raw[:k]], bool((raw[k:] == SENTINEL).all())
+    rc, k, (raw,) = call_sequence(gpu, "pp_motion", depth, w, h, src, prev_args(prev, pls), [("sad", (), "int64")],
+                                  idx, n, nsrc, sls, null)
+    return rc, [int(v) for v in raw[:k]], untouched(raw, k)
 
 
 def _check(gpu, depth, a, idx=None, prev=None, layout="std", player="std", label=""):

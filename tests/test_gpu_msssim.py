@@ -6,16 +6,15 @@ scale-4 window, one window and none, and the seams of the kernel's tiling (a
 wave's 64 and a tile's 256 window columns, a band's 64 window rows, the row
 loop's unroll by 11), all with poisoned pitch padding.  Every call writes into
 a larger, sentinel-filled output and must change [ndist][5][2] alone."""
-import ctypes
 
 import numpy as np
 import pytest
 
 import msssim_ref as R
+from gpu_calls import SENTINEL, call_pair, make as _make
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0x5A5A5A5A5A5A5A5A
 BAR = 1e-9
 _REF = {}
 
@@ -35,52 +34,10 @@ def _terms(a, b, depth):
     return _REF[key]
 
 
-def _make(gpu, depth, data, layout="std", seed=0):
-    """The planes `data` [n, h, w] on the device as an [n, h, w] view.  Layouts:
-    std (pointer, pitch and frame stride on the 16-B grid, at least 16 B of
-    pitch padding), odd (one element off the grid, an odd pitch).  The padding
-    holds random samples of the whole container: poison."""
-    import torch
-    rng = np.random.default_rng(seed + 77)
-    n, h, w = data.shape
-    es = 2 if depth > 8 else 1
-    dt = np.uint16 if es == 2 else np.uint8
-    top = (1 << (8 * es)) - 1
-    if layout == "std":
-        rows, cols, x0, y0 = h + 2, ((w * es + 15) // 16 * 16 + 16) // es, 0, 0
-        if (rows * cols * es) % 16:
-            rows += 1
-    else:
-        rows, cols, x0, y0 = h + 3, (w + 7) | 1, 1, 1
-    big = rng.integers(0, top + 1, (max(n, 1), rows, cols)).astype(dt)
-    big[:n, y0:y0 + h, x0:x0 + w] = data
-    t = torch.from_numpy(big).to(gpu)[:n, y0:y0 + h, x0:x0 + w]
-    on_grid = (t.data_ptr() | t.stride(1) * es | t.stride(0) * es) % 16 == 0
-    assert on_grid == (layout == "std")
-    return t
-
-
-def _call(gpu, depth, w, h, ref, dist, idx=None, nd=None, nr=None, rls=None, dls=None, null=()):
+def _call(gpu, depth, w, h, ref, dist, *args, **kw):
     """pp_ms_ssim itself on a sentinel-filled output of two frames more than it
     needs; returns (rc, out [nd, 5, 2] float64, untouched: everything else kept the sentinel)."""
-    import torch
-    from pixpath import _native, ops
-    L = _native.lib()
-    nd = dist.shape[0] if nd is None else nd
-    nr = ref.shape[0] if nr is None else nr
-    es = dist.element_size()
-    out = torch.full((max(nd, 0) + 2, 5, 2), SENTINEL, dtype=torch.int64, device=gpu)
-    ix = None if idx is None else np.ascontiguousarray(idx, dtype=np.int32)
-    ptr = lambda name, v: None if name in null else ctypes.c_void_p(v)
-    rc = L.pp_ms_ssim(None if "ctx" in null else ops.context(gpu.index).handle, depth, w, h,
-                      ptr("ref", ref.data_ptr()), ref.stride(1) * es if rls is None else rls, ref.stride(0) * es, nr,
-                      ptr("dist", dist.data_ptr()), dist.stride(1) * es if dls is None else dls, dist.stride(0) * es,
-                      nd, None if ix is None else ix.ctypes.data, ptr("out", out.data_ptr()),
-                      ctypes.c_void_p(torch.cuda.current_stream(gpu).cuda_stream))
-    torch.cuda.synchronize(gpu)
-    raw = out.cpu().numpy()
-    n = max(nd, 0) if rc == 0 else 0
-    return rc, raw[:n].view(np.float64), bool((raw[n:] == SENTINEL).all())
+    return call_pair(gpu, "pp_ms_ssim", (5, 2), depth, w, h, ref, dist, *args, **kw)
 
 
 def _check(gpu, depth, a, b, idx=None, rl="std", dl="std", label=""):
