@@ -15,7 +15,7 @@ import os
 
 import numpy as np
 
-from .clips import clip_batches, json_value, planar_format
+from .clips import clip_pair, json_value, map_entries
 
 # kernel geometry (csrc/align.hip), for tests that place sizes on its seams
 LANE_BYTES = 16    # kAlnLaneBytes: bytes a lane loads per piece
@@ -121,9 +121,8 @@ def nominal_advances(k0, n, in_rate, out_rate):
     """d_k for k in [k0, k0 + n): nom[k] - nom[k-1] of the vf_fps map of a
     reference at ``in_rate`` shown at ``out_rate`` (ops.fps_map, taken from a
     long enough clip: the clamp to a last frame never shows), d_0 = 0."""
-    from .metrics import _map_entries
     lo = max(int(k0) - 1, 0)
-    m = _map_entries(lo, int(k0) + int(n) - lo, in_rate, out_rate).astype(np.int64)
+    m = map_entries(lo, int(k0) + int(n) - lo, in_rate, out_rate).astype(np.int64)
     d = np.diff(m, prepend=m[:1])
     return d[int(k0) - lo:]
 
@@ -146,12 +145,12 @@ def _slice(b, lo, hi=None):
 def align_files(ref_path, dist_path, batch=32, lookahead=LOOKAHEAD, min_psnr=MIN_PSNR, flags="bicubic", crop=None,
                 crop_from="yuv422p"):
     """PP-ALIGN-1 of the file ``dist_path`` (the PVS) against ``ref_path`` (the
-    SRC).  Both are read as metrics_of_files reads them (packed CPVS and
-    ``crop`` included) and the reference is brought to the distorted clip's
-    size and format with ops.Scaler when they differ.  The reference frames
-    [cursor, cursor + band) stay resident, frames behind the cursor are
-    dropped; every distorted batch is one ops.sse_band launch (more only after
-    a skip past the band) followed by ``track``.
+    SRC).  The pair is opened by clips.clip_pair (packed CPVS and ``crop``
+    included; the reference is brought to the distorted clip's size and format
+    with ops.Scaler when they differ).  The reference frames [cursor, cursor +
+    band) stay resident, frames behind the cursor are dropped
+    (clips.ReferenceWindow); every distorted batch is one ops.sse_band launch
+    (more only after a skip past the band) followed by ``track``.
 
     Returns a dict: ``map`` int32 [N] (-1 unmatched), ``sse`` int64 [N] (the
     winning SSE, -1 unmatched), ``advance`` (d_k), ``holds`` / ``skips`` /
@@ -159,19 +158,12 @@ def align_files(ref_path, dist_path, batch=32, lookahead=LOOKAHEAD, min_psnr=MIN
     import torch
 
     from . import ops
-    from .frames import FrameBatch
     batch, lookahead = int(batch), int(lookahead)
     if lookahead < 1:
         raise ValueError("lookahead must be at least 1")
     dev = torch.device("cuda", torch.cuda.current_device())
     maps, sses, advs = [], [], []
-    with clip_batches(ref_path, batch) as (ref, _, refs), \
-            clip_batches(dist_path, batch, crop, crop_from, "distorted clip") as (dist, window, dists):
-        rfmt, dfmt = planar_format(ref), planar_format(dist)
-        dw, dh = (dist.w, dist.h) if window is None else window[2:]
-        same = (rfmt.id, ref.w, ref.h) == (dfmt.id, dw, dh)
-        scaler = None if same else ops.Scaler(rfmt, ref.w, ref.h, dfmt, dw, dh, flags=flags, device=dev)
-        win, win0, n_ref, ref_end = None, 0, 0, False  # resident reference frames [win0, n_ref)
+    with clip_pair(ref_path, dist_path, batch, flags, crop, crop_from) as (ref, dist, dfmt, dw, dh, dists, window):
         cursor, k0 = 0, 0
         for d in dists:
             adv = nominal_advances(k0, d.n, ref.rate, dist.rate)
@@ -179,33 +171,16 @@ def align_files(ref_path, dist_path, batch=32, lookahead=LOOKAHEAD, min_psnr=MIN
             r = 0
             while r < d.n:
                 ncand = band(adv[r:], lookahead)
-                while not ref_end and n_ref < cursor + ncand:
-                    nxt = next(refs, None)
-                    if nxt is None:
-                        ref_end = True
-                        break
-                    if scaler is not None:
-                        nxt = scaler(nxt)
-                    keep = min(max(cursor - win0, 0), win.n) if win is not None else 0
-                    if win is None or keep == win.n:
-                        win, win0 = nxt, n_ref
-                    else:
-                        k1 = win.n - keep
-                        nw = FrameBatch(dfmt, dw, dh, k1 + nxt.n, device=dev)
-                        for p in range(3):
-                            nw.view(p)[:k1].copy_(win.view(p)[keep:])
-                            nw.view(p)[k1:].copy_(nxt.view(p))
-                        win, win0 = nw, win0 + keep
-                    n_ref += nxt.n
+                window.extend(cursor + ncand, cursor)  # the band resident, the frames behind the cursor dropped
                 m = d.n - r
-                if win is None:  # an empty reference: nothing can match
+                if window.frames is None:  # an empty reference: nothing can match
                     mp, ws = np.full(m, -1, np.int32), np.full(m, -1, np.int64)
                 else:
-                    rows = ops.sse_band(win, _slice(d, r), [cursor - win0] * m, ncand)
+                    rows = ops.sse_band(window.frames, _slice(d, r), [cursor - window.first] * m, ncand)
                     torch.cuda.current_stream(dev).synchronize()
                     mp, ws, cursor = track(rows.cpu().numpy(), [cursor] * m, adv[r:],
-                                           n_ref if ref_end else UNKNOWN_LENGTH, lookahead, min_psnr, dw, dh,
-                                           dfmt.depth, cursor)
+                                           window.count if window.ended else UNKNOWN_LENGTH, lookahead, min_psnr,
+                                           dw, dh, dfmt.depth, cursor)
                 maps.append(mp)
                 sses.append(ws)
                 r += len(mp)

@@ -1,6 +1,7 @@
-"""Reading a clip file into HBM for `cli metrics`, `cli stats` and `cli
-framecrc`: the reader of a file, the planar format of its frames, the window of
-an AVPVS picture in a CPVS canvas, the loop that streams ``batch`` frames."""
+"""Reading clip files into HBM for the file-level commands: the reader of a
+file, the planar format of its frames, the window of an AVPVS picture in a CPVS
+canvas, the loop that streams ``batch`` frames; a PVS and its SRC as a pair
+with the resident reference frames; the luma reader of a file."""
 import contextlib
 import math
 
@@ -94,6 +95,105 @@ def clip_batches(path, batch, crop=None, crop_from="yuv422p", what="clip", read=
         yield rd, window, batches()
     finally:
         rd.close()
+
+
+def map_entries(k0, n, in_rate, out_rate, n_in=None):
+    """vf_fps entries [k0, k0 + n) of the dist <- ref frame map.  Before the
+    reference's length is known the map of a long enough clip is used: the two
+    agree on every entry below the true clip's end, up to the clamp to its
+    last frame."""
+    from . import ops
+    if n_in is None:
+        n_in = int((k0 + n) * in_rate / out_rate) + 4
+    return ops.fps_map(n_in, in_rate, out_rate)[k0:k0 + n]
+
+
+class ReferenceWindow:
+    """The resident reference frames of a pair: ``frames`` holds frames
+    [first, count) (None before the first batch); ``ended``: the reference has
+    been read to its end, ``count`` is its length.  ``batches``: an iterator of
+    FrameBatches; ``scale``: None, or what brings each, once, to fmt, w, h."""
+
+    def __init__(self, batches, scale, fmt, w, h):
+        self._batches, self._scale, self._geometry = batches, scale, (fmt, w, h)
+        self.frames, self.first, self.count, self.ended = None, 0, 0, False
+
+    def extend(self, upto, behind):
+        """Reads on until ``count`` reaches ``upto`` or the reference ends.
+        Each batch that arrives drops the frames below ``behind``: the tail kept
+        and the batch are copied into a fresh FrameBatch; without a tail the
+        batch itself becomes the window."""
+        from .frames import FrameBatch
+        while not self.ended and self.count < upto:
+            r = next(self._batches, None)
+            if r is None:
+                self.ended = True
+                break
+            if self._scale is not None:
+                r = self._scale(r)
+            tail = max(self.count - max(int(behind), self.first), 0)  # resident frames at or past ``behind``
+            if tail:
+                win, joined = self.frames, FrameBatch(*self._geometry, tail + r.n, device=r.device)
+                for p in range(3):
+                    joined.view(p)[:tail].copy_(win.view(p)[win.n - tail:])
+                    joined.view(p)[tail:].copy_(r.view(p))
+            self.frames = joined if tail else r
+            self.first, self.count = self.count - tail, self.count + r.n
+
+
+@contextlib.contextmanager
+def clip_pair(ref_path, dist_path, batch, flags="bicubic", crop=None, crop_from="yuv422p"):
+    """``as (ref, dist, dfmt, dw, dh, dists, window)``: the readers of a SRC
+    and its PVS (clip_batches; ``crop`` is the PVS's), the planar format and
+    size of the distorted frames, a generator of their batches, and the
+    ReferenceWindow of the reference, through ops.Scaler (``flags``) if it differs."""
+    from . import ops
+    with clip_batches(ref_path, batch) as (ref, _, refs), \
+            clip_batches(dist_path, batch, crop, crop_from, "distorted clip") as (dist, cropped, dists):
+        rfmt, dfmt = planar_format(ref), planar_format(dist)
+        dw, dh = (dist.w, dist.h) if cropped is None else cropped[2:]
+        same = (rfmt.id, ref.w, ref.h) == (dfmt.id, dw, dh)
+        scaler = None if same else ops.Scaler(rfmt, ref.w, ref.h, dfmt, dw, dh, flags=flags)  # on the current device
+        yield ref, dist, dfmt, dw, dh, dists, ReferenceWindow(refs, scaler, dfmt, dw, dh)
+
+
+class LumaOf:
+    """A full-frame pixpath.io reader seen as a luma reader."""
+
+    def __init__(self, rd):
+        self.rd, self.w, self.h, self.depth = rd, rd.w, rd.h, rd.fmt.depth
+        self.luma_bytes = self.w * self.h * (2 if self.depth > 8 else 1)
+        self._buf = None
+
+    def read_into(self, buf, n):
+        fb = self.rd.frame_bytes
+        if self._buf is None or len(self._buf) < n * fb:
+            self._buf = np.empty(n * fb, np.uint8)
+        k = self.rd.read_into(self._buf, n)
+        out = np.frombuffer(memoryview(buf).cast("B"), np.uint8)
+        lb = self.luma_bytes
+        for i in range(k):
+            out[i * lb:(i + 1) * lb] = self._buf[i * fb:i * fb + lb]
+        return k
+
+    def close(self):
+        self.rd.close()
+
+
+def open_luma(videofile, reader=None):
+    """(rd, packed) for the luma of a file.  A v210 or UYVY AVI needs no
+    decoder: rd is its io.PackedAviReader, whose packets go to the GPU as they
+    are, the luma unpacked there.  Otherwise rd is a luma reader: io.LumaReader
+    (y4m / raw seek past chroma, ffmpeg decodes to gray / gray10le) or, of
+    ``reader``, a full-frame pixpath.io reader, its luma plane (LumaOf).  The
+    caller closes rd."""
+    from . import avi, io as pio
+    if reader is not None:
+        return LumaOf(reader), False
+    if isinstance(videofile, str) and videofile.lower().endswith(".avi") \
+            and pio.packed_fourcc(avi.scan(videofile, headers_only=True)[0].get("fourcc")):
+        return pio.PackedAviReader(videofile), True
+    return pio.LumaReader(videofile), False
 
 
 def host_array(outs, tail, dtype):

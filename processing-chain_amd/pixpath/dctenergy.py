@@ -99,33 +99,28 @@ def _packed_batches(rd, batch, dev, window):
 def dct_energy_of_file(videofile, batch=32, reader=None, crop=None, crop_from="yuv422p"):
     """PP-DCTE-1 of the file ``videofile`` on its own: ``summarize``'s dict
     plus ``frames``, ``w``, ``h``, ``bitdepth`` and ``blocks`` (bx, by).  Luma
-    alone is read, as siti.siti_of_file reads it: pixpath.io.LumaReader (y4m /
-    raw seek past chroma, ffmpeg decodes to gray / gray10le), or ``reader``, a
-    full-frame pixpath.io reader whose luma plane is used; the packets of a
-    v210 or UYVY AVI go to the GPU as they are and their luma is unpacked there
-    (``crop`` = (w, h), ``crop_from``: the AVPVS picture inside a CPVS canvas,
-    as stats.stats_of_file's).  ``batch`` frames at a time; a copy of the last
+    alone is read, as clips.open_luma reads it (``reader``: a full-frame
+    pixpath.io reader instead); of a v210 or UYVY AVI, ``crop`` = (w, h) and
+    ``crop_from`` give the AVPVS picture inside a CPVS canvas, as
+    stats.stats_of_file's.  ``batch`` frames at a time; a copy of the last
     luma plane of a batch is the next call's ``prev``, so only frame 0 of the
     file has no difference."""
     import torch
 
-    from . import avi, clips, io as pio, ops, siti
+    from . import clips, ops
     batch = max(1, int(batch))
     dev = torch.device("cuda", torch.cuda.current_device())
-    packed = reader is None and isinstance(videofile, str) and videofile.lower().endswith(".avi") \
-        and pio.packed_fourcc(avi.scan(videofile, headers_only=True)[0].get("fourcc"))
-    if crop is not None and not packed:
-        raise ValueError("crop applies to a packed (v210 / UYVY) clip")
-    if packed:
-        rd = pio.PackedAviReader(videofile)
-        window = None if crop is None else clips.crop_window(rd.w, rd.h, crop[0], crop[1], crop_from)
-        w, h, depth = (rd.w, rd.h) + (rd.fmt.depth,) if window is None else tuple(window[2:]) + (rd.fmt.depth,)
-        batches = _packed_batches(rd, batch, dev, window)
-    else:
-        rd = siti._LumaOf(reader) if reader is not None else pio.LumaReader(videofile)
-        w, h, depth = rd.w, rd.h, rd.depth
-        batches = _host_batches(rd, batch, dev)
+    rd, packed = clips.open_luma(videofile, reader)
     try:
+        if crop is not None and not packed:
+            raise ValueError("crop applies to a packed (v210 / UYVY) clip")
+        if packed:
+            window = None if crop is None else clips.crop_window(rd.w, rd.h, crop[0], crop[1], crop_from)
+            w, h, depth = (rd.w, rd.h) + (rd.fmt.depth,) if window is None else tuple(window[2:]) + (rd.fmt.depth,)
+            batches = _packed_batches(rd, batch, dev, window)
+        else:
+            w, h, depth = rd.w, rd.h, rd.depth
+            batches = _host_batches(rd, batch, dev)
         outs, prev = [], None
         for luma in batches:
             outs.append(ops.dct_energy(luma, depth, prev=prev))

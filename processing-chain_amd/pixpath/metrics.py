@@ -19,7 +19,7 @@ import numpy as np
 
 from . import adm as _adm, banding as _banding, ciede as _ciede, formats, motion as _motion, msssim as _msssim, \
     psnrhvs as _psnrhvs, vif as _vif
-from .clips import clip_batches, crop_window, host_array, json_value, nan_mean, planar_format  # noqa: F401
+from .clips import clip_pair, crop_window, host_array, json_value, map_entries, nan_mean  # noqa: F401
 
 PLANES = ("y", "u", "v")
 # kernel geometry (csrc/metrics.hip), for tests that place sizes on its seams
@@ -190,17 +190,6 @@ def summarize(sse, ssim, fmt, w, h, matched=None, ms_terms=None, vif_terms=None,
     return res
 
 
-def _map_entries(k0, n, in_rate, out_rate, n_in=None):
-    """vf_fps entries [k0, k0 + n) of the dist <- ref frame map.  Before the
-    reference's length is known the map of a long enough clip is used: the two
-    agree on every entry below the true clip's end, up to the clamp to its
-    last frame."""
-    from . import ops
-    if n_in is None:
-        n_in = int((k0 + n) * in_rate / out_rate) + 4
-    return ops.fps_map(n_in, in_rate, out_rate)[k0:k0 + n]
-
-
 def _clip_arrays(outs, empty):
     """The host array of a whole clip for every (trailing shape, dtype) of
     ``empty``, from the tuples of device tensors its batches gave."""
@@ -251,14 +240,7 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, 
     features = [f for f in FEATURES if asked[f.name]]
     batch = int(batch)
     dev = torch.device("cuda", torch.cuda.current_device())
-    with clip_batches(ref_path, batch) as (ref, _, refs), \
-            clip_batches(dist_path, batch, crop, crop_from, "distorted clip") as (dist, window, dists):
-        rfmt, dfmt = planar_format(ref), planar_format(dist)
-        dw, dh = (dist.w, dist.h) if window is None else window[2:]
-        same = (rfmt.id, ref.w, ref.h) == (dfmt.id, dw, dh)
-        scaler = None if same else ops.Scaler(rfmt, ref.w, ref.h, dfmt, dw, dh, flags=flags, device=dev)
-        in_rate, out_rate = ref.rate, dist.rate
-        win, win0, n_ref, ref_end = None, 0, 0, False  # resident reference frames [win0, n_ref), dist geometry
+    with clip_pair(ref_path, dist_path, batch, flags, crop, crop_from) as (ref, dist, dfmt, dw, dh, dists, window):
         outs, k0 = [], 0
         fouts = {f.name: [] for f in features}       # what every batch's enqueue returned, by measurement
         carried = {f.name: None for f in features}   # and what it handed to the next batch's
@@ -266,7 +248,7 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, 
         last = 0  # explicit map: the reference frame an unmatched distorted frame is read against (and not reported)
         for d in dists:
             if explicit is None:
-                m = _map_entries(k0, d.n, in_rate, out_rate)
+                m = map_entries(k0, d.n, ref.rate, dist.rate)
             else:
                 m = explicit[k0:k0 + d.n].copy()
                 if len(m) == 0:
@@ -277,34 +259,18 @@ def metrics_of_files(ref_path, dist_path, batch=32, flags="bicubic", crop=None, 
                     elif m[i] < last:
                         raise ValueError("ref_index goes back from %d to %d at frame %d" % (last, m[i], k0 + i))
                     last = int(m[i])
-            while not ref_end and n_ref <= int(m[-1]):
-                r = next(refs, None)
-                if r is None:
-                    ref_end = True
-                    break
-                if scaler is not None:
-                    r = scaler(r)
-                keep = max(int(m[0]) - win0, 0) if win is not None else 0
-                if win is None or keep >= win.n:
-                    win, win0 = r, n_ref
-                else:
-                    k1 = win.n - keep
-                    nw = FrameBatch(dfmt, dw, dh, k1 + r.n, device=dev)
-                    for p in range(3):
-                        nw.view(p)[:k1].copy_(win.view(p)[keep:])
-                        nw.view(p)[k1:].copy_(r.view(p))
-                    win, win0 = nw, win0 + keep
-                n_ref += r.n
-            if ref_end and explicit is not None:
+            window.extend(int(m[-1]) + 1, int(m[0]))  # the reference frames this batch shows, resident
+            win, n_ref = window.frames, window.count
+            if window.ended and explicit is not None:
                 if int(m[-1]) >= n_ref:
                     raise ValueError("ref_index names frame %d of a reference of %d frames" % (int(m[-1]), n_ref))
-            elif ref_end:  # the reference's length is known now: the map's true end and clamp
-                m = _map_entries(k0, d.n, in_rate, out_rate, n_in=n_ref)
+            elif window.ended:  # the reference's length is known now: the map's true end and clamp
+                m = map_entries(k0, d.n, ref.rate, dist.rate, n_in=n_ref)
             if len(m) == 0 or win is None:
                 break
             if len(m) < d.n:
                 d = FrameBatch(dfmt, dw, dh, len(m), device=d.device, planes=[t[:len(m)] for t in d.planes])
-            idx = m - win0
+            idx = m - window.first
             outs.append(ops.metrics(win, d, ref_index=idx))
             for f in features:
                 tensors, carried[f.name] = f.enqueue(ops, win, d, idx, carried[f.name], options)

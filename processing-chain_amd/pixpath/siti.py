@@ -78,32 +78,18 @@ def siti_summary(si, ti):
 
 
 def siti_of_file(videofile, batch=120, reader=None, normalize=False, with_depth=False):
-    """Per-frame SI/TI of a file: decoded luma only (pixpath.io.LumaReader:
-    y4m/raw seek past chroma, ffmpeg decodes to gray/gray10le), streamed
-    through pinned double buffers (siti_stream).  ``reader``: a full-frame
-    pixpath.io reader instead (its luma plane is used).  A v210 or UYVY AVI
-    needs no decoder: its packets go to the GPU as they are
-    (pixpath.io.PackedAviReader) and the luma is unpacked there
-    (siti_stream_packed; bitdepth 10 / 8).  Returns (si, ti) or, with_depth,
-    (si, ti, bitdepth)."""
-    from . import avi, io as pio
-    if reader is None and isinstance(videofile, str) and videofile.lower().endswith(".avi") \
-            and pio.packed_fourcc(avi.scan(videofile, headers_only=True)[0].get("fourcc")):
-        prd = pio.PackedAviReader(videofile)
-        try:
-            si, ti = siti_stream_packed(prd, batch=batch, normalize=normalize)
-        finally:
-            prd.close()
-        return (si, ti, prd.fmt.depth) if with_depth else (si, ti)
-    if reader is not None:
-        rd = _LumaOf(reader)
-    else:
-        rd = pio.LumaReader(videofile)
+    """Per-frame SI/TI of a file, its luma read as clips.open_luma reads it
+    (``reader``: a full-frame pixpath.io reader instead): decoded luma streams
+    through pinned double buffers (siti_stream), the packets of a v210 or UYVY
+    AVI through siti_stream_packed (bitdepth 10 / 8).  Returns (si, ti) or,
+    with_depth, (si, ti, bitdepth)."""
+    from . import clips
+    rd, packed = clips.open_luma(videofile, reader)
     try:
-        si, ti = siti_stream(rd, batch=batch, normalize=normalize)
+        si, ti = (siti_stream_packed if packed else siti_stream)(rd, batch=batch, normalize=normalize)
     finally:
         rd.close()
-    return (si, ti, rd.depth) if with_depth else (si, ti)
+    return (si, ti, rd.fmt.depth if packed else rd.depth) if with_depth else (si, ti)
 
 
 def siti_stream_packed(rd, batch=120, normalize=False, device=None):
@@ -140,29 +126,6 @@ def siti_stream_packed(rd, batch=120, normalize=False, device=None):
     if not outs:
         return np.zeros(0), np.zeros(0)
     return (torch.cat([o[0] for o in outs]).cpu().numpy(), torch.cat([o[1] for o in outs]).cpu().numpy())
-
-
-class _LumaOf:
-    """A full-frame pixpath.io reader seen as a luma reader."""
-
-    def __init__(self, rd):
-        self.rd, self.w, self.h, self.depth = rd, rd.w, rd.h, rd.fmt.depth
-        self.luma_bytes = self.w * self.h * (2 if self.depth > 8 else 1)
-        self._buf = None
-
-    def read_into(self, buf, n):
-        fb = self.rd.frame_bytes
-        if self._buf is None or len(self._buf) < n * fb:
-            self._buf = np.empty(n * fb, np.uint8)
-        k = self.rd.read_into(self._buf, n)
-        out = np.frombuffer(memoryview(buf).cast("B"), np.uint8)
-        lb = self.luma_bytes
-        for i in range(k):
-            out[i * lb:(i + 1) * lb] = self._buf[i * fb:i * fb + lb]
-        return k
-
-    def close(self):
-        self.rd.close()
 
 
 def siti_stream(rd, batch=120, normalize=False, device=None):

@@ -10,21 +10,14 @@ import numpy as np
 import pytest
 
 import adm_ref as R
-import pyoracle as po
 import synth
+from file_clips import growing_error_pair, last_line as _line, write_cpvs, write_y4m
 from test_gpu_adm import REL
 
 pytestmark = pytest.mark.gpu
 FMT, W, H, N, RATE = "yuv422p10le", 64, 36, 12, 60
 FREEZE = [[0.1, 0.05]]  # frames 6..8 show frame 5
 ADM_KEYS = {"adm2_y", "adm_scales_y", "adm2_y_frames", "adm_scales_y_frames"}
-
-
-def _write(path, frames):
-    from pixpath import io as pio
-    wr = pio.Y4MWriter(path, FMT, W, H, RATE)
-    wr.write(pio.join_planes(synth.batch(frames)))
-    wr.close()
 
 
 def _want(ref, dist):
@@ -37,23 +30,12 @@ def _want(ref, dist):
 @pytest.fixture(scope="module")
 def clips(tmp_path_factory):
     d = tmp_path_factory.mktemp("adm")
-    rng = np.random.default_rng(51)
-    src = [synth.noise_frame(rng, po.YUV422P10LE, W, H) for _ in range(N)]
-    pvs = []
-    for k, f in enumerate(src):  # the luma gets an error growing with k
-        e = 3 * (k + 1)
-        y = np.clip(f[0].astype(np.int64) + rng.integers(-e, e + 1, f[0].shape), 0, 1023).astype(np.uint16)
-        pvs.append([y, f[1], f[2]])
-    paths = {"src": str(d / "src.y4m"), "pvs": str(d / "pvs.y4m"), "dir": d, "src_y": [f[0] for f in src],
+    src, pvs = growing_error_pair(51, FMT, W, H, N)  # the luma gets an error growing with k
+    paths = {"src": write_y4m(d / "src.y4m", FMT, RATE, synth.batch(src)), "dir": d, "src_y": [f[0] for f in src],
              "pvs_planes": synth.batch(pvs)}
-    _write(paths["src"], src)
-    _write(paths["pvs"], pvs)
+    paths["pvs"] = write_y4m(d / "pvs.y4m", FMT, RATE, paths["pvs_planes"])
     paths["want"] = _want([f[0] for f in src], [f[0] for f in pvs])
     return paths
-
-
-def _line(capsys):
-    return json.loads(capsys.readouterr().out.strip().splitlines()[-1])
 
 
 def _compare(d, want):
@@ -137,14 +119,9 @@ def test_aligned_freeze(gpu, clips, capsys):
 
 def test_crop_of_a_cpvs_canvas(gpu, clips, capsys, tmp_path):
     """The PVS padded onto a 64 x 48 v210 canvas: --crop 64x36 scores the picture inside it, as the PVS itself."""
-    from pixpath import avi, cli, metrics, ops
-    from pixpath.frames import FrameBatch
-    packed = ops.cpvs(FrameBatch.from_numpy(FMT, clips["pvs_planes"], device=gpu), 64, 48)
+    from pixpath import cli, metrics
     path = str(tmp_path / "cpvs.avi")
-    wr = avi.AviWriter(path, 64, 48, RATE, fourcc=b"v210")
-    for f in packed.view(0).cpu().numpy():
-        wr.write_packet(np.ascontiguousarray(f).reshape(-1))
-    wr.close()
+    write_cpvs(path, gpu, FMT, clips["pvs_planes"], 64, 48, RATE)
     res = metrics.metrics_of_files(clips["src"], path, crop=(W, H), adm=True, batch=7)
     plain = metrics.metrics_of_files(clips["src"], clips["pvs"], adm=True)
     assert res["frames"] == N

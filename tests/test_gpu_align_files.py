@@ -20,6 +20,7 @@ import pytest
 import align_ref
 import pyoracle as po
 import synth
+from file_clips import last_line as _line, write_y4m
 
 pytestmark = pytest.mark.gpu
 GOLDEN_SPINNER = os.path.join(os.path.dirname(__file__), "golden", "spinner-128-white.png")
@@ -30,25 +31,16 @@ FREEZE = [[0.25, 0.1]]             # frames 15..20 show frame 14
 
 @pytest.fixture(scope="module")
 def clip(tmp_path_factory):
-    from pixpath import io as pio
     d = tmp_path_factory.mktemp("align")
     rng = np.random.default_rng(40)
     frames = [synth.noise_frame(rng, po.YUV422P10LE, W, H) for _ in range(N)]
-    path = str(d / "wo_buffer.y4m")
-    wr = pio.Y4MWriter(path, FMT, W, H, RATE)
-    wr.write(pio.join_planes(synth.batch(frames)))
-    wr.close()
-    return {"dir": d, "path": path, "frames": frames}
+    return {"dir": d, "path": write_y4m(d / "wo_buffer.y4m", FMT, RATE, synth.batch(frames)), "frames": frames}
 
 
 def _psnr(a, b):
     d = a.astype(np.int64) - b.astype(np.int64)
     s = int((d * d).sum())
     return math.inf if s == 0 else 10 * math.log10(1023 * 1023 * d.size / s)
-
-
-def _line(capsys):
-    return json.loads(capsys.readouterr().out.strip().splitlines()[-1])
 
 
 def test_stalled_clip(gpu, clip, capsys):
@@ -134,13 +126,9 @@ def test_plain_metrics_unchanged(gpu, clip, capsys):
     """Without --align `cli metrics` prints what metrics_of_files, called as
     before, gives; an identity map gives the same numbers."""
     from pixpath import align, cli, metrics
-    other = str(clip["dir"] / "noisy.y4m")
-    from pixpath import io as pio
     rng = np.random.default_rng(41)
     frames = [synth.noise_frame(rng, po.YUV422P10LE, W, H) for _ in range(N)]
-    wr = pio.Y4MWriter(other, FMT, W, H, RATE)
-    wr.write(pio.join_planes(synth.batch(frames)))
-    wr.close()
+    other = write_y4m(clip["dir"] / "noisy.y4m", FMT, RATE, synth.batch(frames))
     res = metrics.metrics_of_files(clip["path"], other, batch=32, flags="bicubic")
     capsys.readouterr()
     assert cli.main(["metrics", "--ref", clip["path"], "--input", other, "--per-frame"]) == 0

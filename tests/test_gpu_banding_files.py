@@ -11,6 +11,8 @@ import pytest
 
 import banding_ref as R
 import pyoracle as po
+import synth
+from file_clips import last_line, write_packed_avi, write_y4m
 
 pytestmark = pytest.mark.gpu
 FMT, W, H, CW, CH, N = "yuv422p10le", 64, 48, 64, 60, 5
@@ -24,11 +26,7 @@ def _chroma(n=1):
 
 
 def _write_y4m(path, lumas):
-    from pixpath import io as pio
-    import synth
-    wr = pio.Y4MWriter(path, FMT, W, H, 60)
-    wr.write(pio.join_planes(synth.batch([[y, _chroma(), _chroma()] for y in lumas])))
-    wr.close()
+    write_y4m(path, FMT, 60, synth.batch([[y, _chroma(), _chroma()] for y in lumas]))
 
 
 @pytest.fixture(scope="module")
@@ -82,14 +80,10 @@ def test_ffv1_avi(gpu, clip, tmp_path, capsys):
 
 
 def test_v210_cpvs_with_and_without_crop(gpu, clip, tmp_path, capsys):
-    from pixpath import avi, banding, cli
+    from pixpath import banding, cli
     luma, frames = clip
     padded = [po.pad(po.YUV422P10LE, f, CW, CH, 0, 6) for f in frames]
-    path = str(tmp_path / "cpvs.avi")
-    wr = avi.AviWriter(path, CW, CH, 60, fourcc=b"v210")
-    for f in padded:
-        wr.write_packet(np.ascontiguousarray(po.v210_pack(f)).reshape(-1))
-    wr.close()
+    path = write_packed_avi(tmp_path / "cpvs.avi", b"v210", CW, CH, 60, [po.v210_pack(f) for f in padded])
     got = banding.banding_of_file(path, batch=4, window=7)
     assert (got["w"], got["h"]) == (CW, CH)
     _same(got, _pooled(np.stack([f[0] for f in padded]), 7))
@@ -144,7 +138,7 @@ def test_without_the_flag_the_line_is_unchanged(gpu, clip, tmp_path, capsys):
     assert line == json.dumps(metrics.report(res, ref, dist, per_frame=True))
     assert set(json.loads(line)) == BASE_KEYS  # exactly the keys of PP-METRIC-1
     assert cli.main(["metrics", "--ref", ref, "--input", dist, "--banding", "--per-frame"]) == 0
-    with_flag = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+    with_flag = last_line(capsys)
     for k, v in json.loads(line).items():  # the flag only adds keys
         assert with_flag[k] == v
     assert set(with_flag) - set(json.loads(line)) == BAND_KEYS | {k + "_frames" for k in BAND_KEYS}

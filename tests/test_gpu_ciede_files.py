@@ -12,19 +12,13 @@ import pytest
 import ciede_ref
 import pyoracle as po
 import synth
+from file_clips import last_line as _line, write_cpvs, write_y4m
 from test_gpu_ciede import MARGIN, RTOL
 
 pytestmark = pytest.mark.gpu
 FMT, W, H, N, RATE = "yuv422p10le", 64, 36, 12, 60
 FREEZE = [[0.1, 0.05]]  # frames 6..8 show frame 5
 CIEDE_KEYS = {"delta_e", "delta_e_max", "ciede2000", "delta_e_frames", "delta_e_max_frames", "ciede2000_frames"}
-
-
-def _write(path, frames):
-    from pixpath import io as pio
-    wr = pio.Y4MWriter(path, FMT, W, H, RATE)
-    wr.write(pio.join_planes(synth.batch(frames)))
-    wr.close()
 
 
 def _want(ref, dist, weights=(1.0, 1.0, 1.0)):
@@ -44,15 +38,11 @@ def clips(tmp_path_factory):
         e = 2 * (k + 1)
         pvs.append([np.clip(p.astype(np.int64) + rng.integers(-(e if i else 1), (e if i else 1) + 1, p.shape), 0, 1023)
                     .astype(np.uint16) for i, p in enumerate(f)])
-    paths = {"src": str(d / "src.y4m"), "pvs": str(d / "pvs.y4m"), "dir": d, "src_frames": src, "pvs_frames": pvs}
-    _write(paths["src"], src)
-    _write(paths["pvs"], pvs)
+    paths = {"src": write_y4m(d / "src.y4m", FMT, RATE, synth.batch(src)),
+             "pvs": write_y4m(d / "pvs.y4m", FMT, RATE, synth.batch(pvs)), "dir": d, "src_frames": src,
+             "pvs_frames": pvs}
     paths["want"] = _want(src, pvs)
     return paths
-
-
-def _line(capsys):
-    return json.loads(capsys.readouterr().out.strip().splitlines()[-1])
 
 
 def _compare(d, want):
@@ -148,14 +138,9 @@ def test_aligned_stall(gpu, clips, capsys):
 
 def test_crop_of_a_v210_cpvs(gpu, clips, capsys, tmp_path):
     """The PVS padded onto a 64 x 48 v210 canvas: --crop 64x36 scores the picture inside it, as the PVS itself."""
-    from pixpath import avi, cli, metrics, ops
-    from pixpath.frames import FrameBatch
-    packed = ops.cpvs(FrameBatch.from_numpy(FMT, synth.batch(clips["pvs_frames"]), device=gpu), 64, 48)
+    from pixpath import cli, metrics
     path = str(tmp_path / "cpvs.avi")
-    wr = avi.AviWriter(path, 64, 48, RATE, fourcc=b"v210")
-    for f in packed.view(0).cpu().numpy():
-        wr.write_packet(np.ascontiguousarray(f).reshape(-1))
-    wr.close()
+    write_cpvs(path, gpu, FMT, synth.batch(clips["pvs_frames"]), 64, 48, RATE)
     res = metrics.metrics_of_files(clips["src"], path, crop=(W, H), ciede=True, batch=7)
     plain = metrics.metrics_of_files(clips["src"], clips["pvs"], ciede=True)
     assert res["frames"] == N

@@ -13,6 +13,7 @@ import pytest
 import dctenergy_ref as R
 import pyoracle as po
 import synth
+from file_clips import write_packed_avi, write_y4m
 
 pytestmark = pytest.mark.gpu
 FMT, W, H, CW, CH, N = "yuv422p10le", 96, 70, 144, 80, 7
@@ -30,19 +31,8 @@ def clip():
     return {"frames": frames, "luma": luma, "rows": rows, "pooled": R.pool(rows, W, H)}
 
 
-def _y4m(path, frames, w=W, h=H):
-    from pixpath import io as pio
-    wr = pio.Y4MWriter(path, FMT, w, h, 60)
-    wr.write(pio.join_planes(synth.batch(frames)))
-    wr.close()
-
-
 def _v210(path, frames, w, h):
-    from pixpath import avi
-    wr = avi.AviWriter(path, w, h, 60, fourcc=b"v210")
-    for f in frames:
-        wr.write_packet(np.ascontiguousarray(po.v210_pack(f)).reshape(-1))
-    wr.close()
+    write_packed_avi(path, b"v210", w, h, 60, [po.v210_pack(f) for f in frames])
 
 
 def _same(res, pooled):
@@ -55,7 +45,7 @@ def _same(res, pooled):
 def test_planar_clip_across_batch_seams(gpu, clip, tmp_path):
     from pixpath import dctenergy, io as pio
     path = str(tmp_path / "src.y4m")
-    _y4m(path, clip["frames"])
+    write_y4m(path, FMT, 60, synth.batch(clip["frames"]))
     E, T, L = clip["pooled"]
     assert T[0] == 0.0 and T[3] == 0.0 and min(T[1:3] + T[4:]) > 0.0 and min(E) > 0.0  # frame 3 repeats frame 2
     for batch in (1, 3, 32):  # the carried prev across batch seams changes nothing

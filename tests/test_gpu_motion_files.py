@@ -14,6 +14,7 @@ import pytest
 import motion_ref as R
 import pyoracle as po
 import synth
+from file_clips import last_line as _line, write_y4m
 
 pytestmark = pytest.mark.gpu
 FMT, W, H, N, RATE = "yuv422p10le", 64, 36, 12, 60
@@ -22,11 +23,8 @@ BASE_KEYS = {"ref", "file", "frames", "spec"} | {"%s_%s%s" % (kind, name, tail) 
                                                   for name in ("y", "u", "v", "all") for tail in ("", "_frames")}
 
 
-def _write(path, frames, w=W, h=H, rate=RATE):
-    from pixpath import io as pio
-    wr = pio.Y4MWriter(path, FMT, w, h, rate)
-    wr.write(pio.join_planes(synth.batch(frames)))
-    wr.close()
+def _write(path, frames, rate=RATE):
+    write_y4m(path, FMT, rate, synth.batch(frames))
 
 
 @pytest.fixture(scope="module")
@@ -44,10 +42,6 @@ def clips(tmp_path_factory):
     paths["sad"] = R.sad(paths["src_y"], 10)
     paths["motion"] = R.motion(paths["sad"], W, H)
     return paths
-
-
-def _line(capsys):
-    return json.loads(capsys.readouterr().out.strip().splitlines()[-1])
 
 
 def _same(a, b):
@@ -91,7 +85,7 @@ def test_reference_of_another_size_goes_through_the_scaler(gpu, clips, tmp_path)
     rng = np.random.default_rng(62)
     big = [synth.smooth_frame(t, po.YUV422P10LE, 2 * W, 2 * H) for t in range(N)]
     ref = str(tmp_path / "big.y4m")
-    _write(ref, big, w=2 * W, h=2 * H)
+    _write(ref, big)
     scaled = ops.Scaler(FMT, 2 * W, 2 * H, FMT, W, H, flags="bicubic")(
         FrameBatch.from_numpy(FMT, synth.batch(big), device=gpu))
     torch.cuda.synchronize(gpu)

@@ -11,8 +11,8 @@ import numpy as np
 import pytest
 
 import msssim_ref as R
-import pyoracle as po
 import synth
+from file_clips import growing_error_pair, last_line as _line, write_y4m
 
 pytestmark = pytest.mark.gpu
 GOLDEN_SPINNER = os.path.join(os.path.dirname(__file__), "golden", "spinner-128-white.png")
@@ -20,31 +20,15 @@ FMT, W, H, N, RATE = "yuv422p10le", 180, 176, 24, 60
 FREEZE = [[0.2, 0.1]]  # frames 12..17 show frame 11
 
 
-def _write(path, frames):
-    from pixpath import io as pio
-    wr = pio.Y4MWriter(path, FMT, W, H, RATE)
-    wr.write(pio.join_planes(synth.batch(frames)))
-    wr.close()
-
-
 @pytest.fixture(scope="module")
 def clips(tmp_path_factory):
     d = tmp_path_factory.mktemp("msssim")
-    rng = np.random.default_rng(50)
-    src = [synth.noise_frame(rng, po.YUV422P10LE, W, H) for _ in range(N)]
-    pvs = []
-    for k, f in enumerate(src):  # the luma gets an error growing with k; frame 0 stays identical
-        y = np.clip(f[0].astype(np.int64) + rng.integers(-3 * k, 3 * k + 1, f[0].shape), 0, 1023).astype(np.uint16)
-        pvs.append([y, f[1], f[2]])
-    paths = {"src": str(d / "src.y4m"), "pvs": str(d / "pvs.y4m"), "dir": d}
-    _write(paths["src"], src)
-    _write(paths["pvs"], pvs)
+    # the luma gets an error growing with k; frame 0 stays identical
+    src, pvs = growing_error_pair(50, FMT, W, H, N, error=lambda k: 3 * k)
+    paths = {"src": write_y4m(d / "src.y4m", FMT, RATE, synth.batch(src)),
+             "pvs": write_y4m(d / "pvs.y4m", FMT, RATE, synth.batch(pvs)), "dir": d}
     paths["want"] = np.stack([R.terms(src[k][0], pvs[k][0], 10) for k in range(N)])
     return paths
-
-
-def _line(capsys):
-    return json.loads(capsys.readouterr().out.strip().splitlines()[-1])
 
 
 def test_cli_metrics_ms_ssim(gpu, clips, capsys):

@@ -14,6 +14,7 @@ import pytest
 import psnrhvs_ref
 import pyoracle as po
 import synth
+from file_clips import last_line as _line, write_y4m
 from pixpath import psnrhvs
 from test_gpu_psnrhvs import RTOL
 
@@ -24,13 +25,6 @@ EXPLICIT = [0, 0, -1, 1, 2, 2, 3]  # one unmatched frame, never going back
 HVS_KEYS = set(psnrhvs.KEYS) | {"hvs_step", "hvs_blocks"} | {k + "_frames" for k in psnrhvs.KEYS}
 
 
-def _write(path, frames, rate):
-    from pixpath import io as pio
-    wr = pio.Y4MWriter(path, FMT, W, H, rate)
-    wr.write(pio.join_planes(synth.batch(frames)))
-    wr.close()
-
-
 @pytest.fixture(scope="module")
 def clips(tmp_path_factory):
     d = tmp_path_factory.mktemp("psnrhvs")
@@ -38,10 +32,8 @@ def clips(tmp_path_factory):
     src = [synth.smooth_frame(3 * t, po.YUV420P, W, H) for t in range(N_REF)]
     pvs = [[np.clip(p.astype(np.int64) + rng.integers(-6, 7, p.shape), 0, 255).astype(np.uint8) for p in src[k // 2]]
            for k in range(N_DIST)]
-    paths = {"src": str(d / "src.y4m"), "pvs": str(d / "pvs.y4m"), "src_frames": src, "pvs_frames": pvs}
-    _write(paths["src"], src, REF_RATE)
-    _write(paths["pvs"], pvs, DIST_RATE)
-    return paths
+    return {"src": write_y4m(d / "src.y4m", FMT, REF_RATE, synth.batch(src)),
+            "pvs": write_y4m(d / "pvs.y4m", FMT, DIST_RATE, synth.batch(pvs)), "src_frames": src, "pvs_frames": pvs}
 
 
 def _want(clips, ref_index, step):
@@ -50,10 +42,6 @@ def _want(clips, ref_index, step):
     sums = psnrhvs_ref.psnr_hvs(synth.batch(clips["src_frames"]), synth.batch(clips["pvs_frames"]), step,
                                 np.maximum(idx, 0))
     return psnrhvs.summarize(sums, W, H, idx >= 0, FMT, step)
-
-
-def _line(capsys):
-    return json.loads(capsys.readouterr().out.strip().splitlines()[-1])
 
 
 def _compare(d, want):

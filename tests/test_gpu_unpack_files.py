@@ -8,6 +8,7 @@ import pytest
 
 import pyoracle as po
 import synth
+from file_clips import write_cpvs, write_packed_avi, write_y4m
 import unpack_ref
 
 pytestmark = pytest.mark.gpu
@@ -18,21 +19,12 @@ def _clip(fmt, w, h, n, t0=0):
     return synth.batch([synth.smooth_frame(t0 + t, po.FMT_BY_NAME[fmt], w, h) for t in range(n)])
 
 
-def _write_y4m(path, fmt, planes, rate=60):
-    from pixpath import io as pio
-    wr = pio.Y4MWriter(str(path), fmt, planes[0].shape[2], planes[0].shape[1], rate)
-    wr.write(np.ascontiguousarray(pio.join_planes(planes)))
-    wr.close()
-    return str(path)
+def _write_y4m(path, fmt, planes):
+    return write_y4m(path, fmt, 60, planes)
 
 
-def _write_avi(path, fourcc, w, h, packets, rate=60):
-    from pixpath import avi
-    wr = avi.AviWriter(str(path), w, h, rate, fourcc=fourcc)
-    for p in packets:
-        wr.write_packet(np.ascontiguousarray(p).reshape(-1))
-    wr.close()
-    return str(path)
+def _write_avi(path, fourcc, w, h, packets):
+    return write_packed_avi(path, fourcc, w, h, 60, packets)
 
 
 def _perturb(planes, depth, seed=5):
@@ -43,12 +35,8 @@ def _perturb(planes, depth, seed=5):
 
 def _make_cpvs(gpu, tmp_path, fmt, planes, W, H):
     """ops.cpvs of the AVPVS onto the W x H canvas, written as an AVI; returns (path, packed frames)."""
-    from pixpath import ops
-    from pixpath.frames import FrameBatch
-    packed = ops.cpvs(FrameBatch.from_numpy(fmt, planes, device=gpu), W, H)
-    frames = packed.view(0).cpu().numpy()
-    fourcc = b"v210" if packed.fmt.name == "v210" else b"UYVY"
-    return _write_avi(tmp_path / ("cpvs_%s_%d.avi" % (fmt, H)), fourcc, W, H, frames), frames
+    path = str(tmp_path / ("cpvs_%s_%d.avi" % (fmt, H)))
+    return path, write_cpvs(path, gpu, fmt, planes, W, H, 60)
 
 
 def _same(got, want):
