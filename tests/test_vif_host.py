@@ -134,6 +134,28 @@ def test_near_branch_counter():
     assert R.near_branch(c, c, 8) == [40 * 33, 20 * 16, 10 * 8, 5 * 4]  # sigma12 = 0 everywhere
 
 
+@pytest.mark.parametrize("depth", [8, 10])
+def test_separable_and_direct_agree(depth):
+    """terms_separable (what tools/vif_bench.py checks the GPU against) and the
+    direct form sum the same fp64 products in another order.  The largest
+    relative difference of a sum on these inputs is 3.3e-13 (3.0e-13 at 8 bits,
+    3.3e-13 at 10: the variances are differences of nearly equal numbers, which
+    magnifies the rounding of either order); the bar is 8 times that, for numpy
+    builds whose einsum or vector width sums in yet another order.  A wrong tap
+    or a window off by one moves a sum by 1e-3 or more."""
+    cases = (("small_error", 40, 33, 4), ("small_error", 37, 29, 1),  # odd height; odd width and height
+             ("noise", 15, 16, 0), ("small_error", 9, 9, 3),  # scale 3 / scales 1 to 3 do not exist
+             ("smooth_noise", 72, 56, 2), ("noise", 64, 48, 2))
+    for name, w, h, seed in cases:
+        a, b = R.content(name, depth, w, h, seed=seed)
+        assert not any(R.near_branch(a, b, depth)), (name, w, h)  # no position where num jumps
+        d, s = R.terms(a, b, depth), R.terms_separable(a, b, depth)
+        there = ~np.isnan(d)
+        assert np.array_equal(there, ~np.isnan(s)) and there[:len(vif.scale_sizes(w, h))].all()
+        assert there.all(axis=1).sum() == there.any(axis=1).sum() == len(vif.scale_sizes(w, h))
+        assert np.abs(s[there] / d[there] - 1).max() <= 8 * 3.3e-13, (name, w, h)
+
+
 def _fake(n=3):
     sse = np.array([[640, 64, 16]] * n, np.int64)
     ssim = np.array([[0.75, 0.5, 0.5]] * n)

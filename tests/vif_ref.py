@@ -2,7 +2,11 @@
 text in the direct 2-D form: every position's five quantities as the N x N
 samples of the `reflect`-padded plane under the outer-product weight.  It
 shares nothing with the kernel's separable order (csrc/vif.hip).  The pyramid
-uses the same direct form and keeps the even rows and columns."""
+uses the same direct form and keeps the even rows and columns.  `separable`
+applies the window along rows, then along columns, everywhere the direct form
+applies the 2-D one: the same values up to the order of the fp64 sums, fast
+enough for a 1920x1080 plane (`terms_separable`, what tools/vif_bench.py
+checks the GPU against)."""
 import math
 
 import numpy as np
@@ -24,33 +28,37 @@ def exists(p, s):
     return min(p.shape) >= TAPS[s] // 2 + 1
 
 
-def filt(p, s):
+def filt(p, s, separable=False):
     """Plane p under the 2-D window of scale s, mirrored borders: same shape."""
     g = window(s)
     r = TAPS[s] // 2
     q = np.pad(p, r, mode="reflect")
+    if separable:
+        rows = sum(g[i] * q[:, i:i + p.shape[1]] for i in range(TAPS[s]))
+        return sum(g[i] * rows[i:i + p.shape[0]] for i in range(TAPS[s]))
     return np.einsum("ijkl,kl->ij", sliding_window_view(q, (TAPS[s], TAPS[s])), np.outer(g, g))
 
 
-def levels(x, depth):
+def levels(x, depth, separable=False):
     """The scales of plane x that exist, as fp64 planes on the 8-bit scale."""
     p = np.asarray(x).astype(np.float64) / float(1 << (depth - 8))
     out = []
     for s in range(SCALES):
         if s:
-            p = filt(p, s)[0:2 * (p.shape[0] // 2):2, 0:2 * (p.shape[1] // 2):2]
+            p = filt(p, s, separable)[0:2 * (p.shape[0] // 2):2, 0:2 * (p.shape[1] // 2):2]
         if not exists(p, s):
             break
         out.append(p)
     return out
 
 
-def moments(pa, pb, s):
+def moments(pa, pb, s, separable=False):
     """sigma1^2, sigma2^2, sigma12 of every position of scale s (clamped as the spec says)."""
-    mu1, mu2 = filt(pa, s), filt(pb, s)
-    s1 = np.maximum(filt(pa * pa, s) - mu1 * mu1, 0.0)
-    s2 = np.maximum(filt(pb * pb, s) - mu2 * mu2, 0.0)
-    s12 = filt(pa * pb, s) - mu1 * mu2
+    f = lambda p: filt(p, s, separable)
+    mu1, mu2 = f(pa), f(pb)
+    s1 = np.maximum(f(pa * pa) - mu1 * mu1, 0.0)
+    s2 = np.maximum(f(pb * pb) - mu2 * mu2, 0.0)
+    s12 = f(pa * pb) - mu1 * mu2
     return s1, s2, s12
 
 
@@ -76,15 +84,20 @@ def position_terms(s1, s2, s12):
     return num, den
 
 
-def terms(a, b, depth):
+def terms(a, b, depth, separable=False):
     """[4][2]: sum of num and sum of den of every scale of planes a (reference)
     and b; NaN for a scale that does not exist and every later one."""
     out = np.full((SCALES, 2), np.nan)
-    la, lb = levels(a, depth), levels(b, depth)
+    la, lb = levels(a, depth, separable), levels(b, depth, separable)
     for s in range(len(la)):
-        num, den = position_terms(*moments(la[s], lb[s], s))
+        num, den = position_terms(*moments(la[s], lb[s], s, separable))
         out[s] = [float(num.sum()), float(den.sum())]
     return out
+
+
+def terms_separable(a, b, depth):
+    """The same values with every window applied along rows, then along columns."""
+    return terms(a, b, depth, separable=True)
 
 
 def near_branch(a, b, depth):

@@ -20,30 +20,9 @@ gate; it fails without a GPU.
 
   python tools/align_bench.py [--frames 600] [--out profiles/align/NAME.json]
 """
-import argparse
-import json
-import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "processing-chain_amd"))
-
-
-def timed(fn, warmup, iters):
-    import torch
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(iters):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return {"avg_ms": round(sum(ms) / len(ms), 3), "min_ms": round(min(ms), 3), "max_ms": round(max(ms), 3),
-            "passes": len(ms)}
+import callbench
 
 
 def one_depth(fmt, a, dev):
@@ -52,17 +31,9 @@ def one_depth(fmt, a, dev):
 
     from pixpath import ops
     from pixpath.frames import FrameBatch
-    w, h, n = 1920, 1080, a.frames
+    w, h, n = callbench.W, callbench.H, a.frames
     ten = fmt.endswith("10le")
-    lo, hi = (64, 941) if ten else (16, 236)
-    ref, dist = FrameBatch(fmt, w, h, n, device=dev), FrameBatch(fmt, w, h, n, device=dev)
-    for p in range(3):
-        rp, dp = (t.planes[p].view(torch.int16) if ten else t.planes[p] for t in (ref, dist))
-        for k in range(n):  # frame by frame: no batch-sized temporaries
-            r = torch.randint(lo, hi, rp[k].shape, dtype=torch.int16, device=dev)
-            rp[k].copy_(r)
-            dp[k].copy_((r + torch.randint(-8, 9, r.shape, dtype=torch.int16, device=dev)).clamp_(0, 1023 if ten else 255))
-    torch.cuda.synchronize()
+    ref, dist = callbench.noise_pair(fmt, n, dev)
     batches = [(k0, min(a.batch, n - k0)) for k0 in range(0, n, a.batch)]
     cut = lambda k0, m: FrameBatch(fmt, w, h, m, planes=[t[k0:k0 + m] for t in dist.planes])
     parts = [(k0, m, cut(k0, m), min(a.band, n - k0)) for k0, m in batches]  # (first, frames, batch, candidates that exist)
@@ -90,8 +61,8 @@ def one_depth(fmt, a, dev):
                     raise SystemExit("align_bench: %s batch %d candidate %d differs from pp_metrics" % (fmt, k0, c))
             elif not (got[:, c] == -1).all():
                 raise SystemExit("align_bench: %s batch %d candidate %d should be absent" % (fmt, k0, c))
-    new = timed(new_pass, a.warmup, a.iters)
-    base = timed(base_pass, 1, a.base_iters)
+    new = callbench.timed(new_pass, a.warmup, a.iters, count="passes")
+    base = callbench.timed(base_pass, 1, a.base_iters, count="passes")
     cands = sum(m * live for _, m, _, live in parts)
     es = 2 if ten else 1
     return {"fmt": fmt, "new": new, "baseline": base, "baseline_over_new": round(base["avg_ms"] / new["avg_ms"], 2),
@@ -100,31 +71,18 @@ def one_depth(fmt, a, dev):
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--frames", type=int, default=600)
+    ap = callbench.parser(600, 2, 10)
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--band", type=int, default=96)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--base-iters", type=int, default=3)
-    ap.add_argument("--out", default=None)
     a = ap.parse_args(argv)
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("align_bench: no GPU visible (a timing needs the MI355X)")
-    dev = torch.device("cuda", 0)
-    torch.manual_seed(910)
-    res = {"tool": "align_bench", "device": torch.cuda.get_device_name(0), "w": 1920, "h": 1080, "frames": a.frames,
-           "batch": a.batch, "band": a.band, "warmup": a.warmup,
-           "timer": "HIP events around one pass over the clip: every pp_frame_sse_band launch (align_kernel + "
-                    "align_finalize) / every pp_metrics call (metrics_kernel + metrics_finalize) of the pass",
-           "depths": [one_depth(f, a, dev) for f in ("yuv420p", "yuv420p10le")]}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    dev = callbench.require_gpu("align_bench", seed=910)
+    res = callbench.header(
+        "align_bench", a, ("w", "h", "frames", "batch", "band", "warmup"),
+        timer="HIP events around one pass over the clip: every pp_frame_sse_band launch (align_kernel + "
+              "align_finalize) / every pp_metrics call (metrics_kernel + metrics_finalize) of the pass",
+        depths=[one_depth(f, a, dev) for f in ("yuv420p", "yuv420p10le")])
+    callbench.emit(res, a.out)
     return 0
 
 

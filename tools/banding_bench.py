@@ -21,35 +21,13 @@ Prints one JSON line; a measurement, not a gate; it fails without a GPU.
 
   python tools/banding_bench.py [--frames 600] [--out profiles/banding/NAME.json]
 """
-import argparse
-import json
-import os
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "processing-chain_amd"))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import callbench
 
 CHECKED = 2  # frames compared with the restatement per content and depth
 CONTENTS = ("banded", "noise", "constant")
-
-
-def timed(fn, warmup, iters):
-    import torch
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(iters):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return {"avg_ms": round(sum(ms) / len(ms), 3), "min_ms": round(min(ms), 3), "max_ms": round(max(ms), 3),
-            "launches": len(ms)}
 
 
 def fill(src, content, ten, dev):
@@ -77,7 +55,7 @@ def one(fmt, content, a, dev):
     import banding_ref
     from pixpath import banding, ops
     from pixpath.frames import FrameBatch
-    w, h, n = 1920, 1080, a.frames
+    w, h, n = callbench.W, callbench.H, a.frames
     ten = fmt.endswith("10le")
     depth = 10 if ten else 8
     window = banding.default_window(w, h)
@@ -104,9 +82,9 @@ def one(fmt, content, a, dev):
     if not np.array_equal(got, want):
         raise SystemExit("banding_bench: %s %s differs from the restatement" % (fmt, content))
     val = banding.summarize(keep["banding"].cpu().numpy())["mean"]
-    bd = timed(banding_pass, a.warmup, a.iters)
-    ms = timed(ms_pass, a.warmup, a.iters)
-    st = timed(stats_pass, a.warmup, a.iters)
+    bd = callbench.timed(banding_pass, a.warmup, a.iters)
+    ms = callbench.timed(ms_pass, a.warmup, a.iters)
+    st = callbench.timed(stats_pass, a.warmup, a.iters)
     return {"fmt": fmt, "content": content, "window": window, "banding_y": val["banding_y"], "banding": bd,
             "ms_ssim": ms, "stats": st, "us_per_frame": round(bd["avg_ms"] * 1e3 / n, 2),
             "banding_over_ms_ssim": round(bd["avg_ms"] / ms["avg_ms"], 3),
@@ -115,28 +93,15 @@ def one(fmt, content, a, dev):
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--frames", type=int, default=600)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--iters", type=int, default=10)
-    ap.add_argument("--out", default=None)
+    ap = callbench.parser(600, 2, 10)
     a = ap.parse_args(argv)
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("banding_bench: no GPU visible (a timing needs the MI355X)")
-    dev = torch.device("cuda", 0)
-    torch.manual_seed(910)
-    res = {"tool": "banding_bench", "device": torch.cuda.get_device_name(0), "w": 1920, "h": 1080, "frames": a.frames,
-           "warmup": a.warmup,
-           "timer": "HIP events around one call over the clip: every launch of pp_banding / of pp_ms_ssim (the clip "
-                    "against itself) / of pp_frame_stats (three planes, histograms)",
-           "runs": [one(f, c, a, dev) for f in ("yuv420p", "yuv420p10le") for c in CONTENTS]}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    dev = callbench.require_gpu("banding_bench", seed=910)
+    res = callbench.header(
+        "banding_bench", a,
+        timer="HIP events around one call over the clip: every launch of pp_banding / of pp_ms_ssim (the clip "
+              "against itself) / of pp_frame_stats (three planes, histograms)",
+        runs=[one(f, c, a, dev) for f in ("yuv420p", "yuv420p10le") for c in CONTENTS])
+    callbench.emit(res, a.out)
     return 0
 
 

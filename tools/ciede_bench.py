@@ -28,35 +28,12 @@ Prints one JSON line; a measurement, not a gate; it fails without a GPU.
 
   python tools/ciede_bench.py [--frames 600] [--out profiles/ciede/NAME.json]
 """
-import argparse
-import json
-import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "processing-chain_amd"))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import callbench
 
 FP64_INSTR_POSITION = 2452  # 2466 v_*_f64 in ciede_kernel's disassembly less the 14 of the reduction
-FP64_ISSUE_RATE = 256 * 4 * 16 * 2.4e9
-W, H = 1920, 1080
-
-
-def timed(fn, warmup, iters):
-    import torch
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(iters):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return {"avg_ms": round(sum(ms) / len(ms), 3), "min_ms": round(min(ms), 3), "max_ms": round(max(ms), 3),
-            "launches": len(ms)}
+W, H = callbench.W, callbench.H
 
 
 def fill(kind, fmt, n, dev):
@@ -119,22 +96,22 @@ def one_format(fmt, a, dev):
         torch.cuda.synchronize()
         got = keep["ciede"].cpu().numpy()
         worst = check(fmt, ref, dist, got)
-        t = timed(ciede_pass, a.warmup, a.iters)
+        t = callbench.timed(ciede_pass, a.warmup, a.iters)
         px = n * W * H
         entry = {"ciede": t, "ns_per_pixel": round(t["avg_ms"] * 1e6 / px, 4), "restatement_max_rel": worst,
                  "mean_delta_e": float(got[:, 0].mean() / (W * H))}
         if kind != "identical":
             rate = px * FP64_INSTR_POSITION / (t["avg_ms"] * 1e-3)
             entry["fp64_instr_per_s_upper"] = float("%.4g" % rate)
-            entry["share_of_fp64_issue_rate_upper"] = round(rate / FP64_ISSUE_RATE, 3)
+            entry["share_of_fp64_issue_rate_upper"] = round(rate / callbench.FP64_ISSUE_RATE, 3)
         else:
             es = 2 if fmt.endswith("10le") else 1
             traffic = 2 * n * sum(r * c for r, c in formats.plane_shapes(fmt, W, H)) * es
             entry["algorithmic_bytes"] = traffic
             entry["tb_per_s"] = round(traffic / (t["avg_ms"] * 1e-3) / 1e12, 3)
         if kind == "noise":
-            vf = timed(lambda: keep.__setitem__("vif", ops.vif(ref, dist)), a.warmup, a.iters)
-            met = timed(lambda: keep.__setitem__("met", ops.metrics(ref, dist)), a.warmup, a.iters)
+            vf = callbench.timed(lambda: keep.__setitem__("vif", ops.vif(ref, dist)), a.warmup, a.iters)
+            met = callbench.timed(lambda: keep.__setitem__("met", ops.metrics(ref, dist)), a.warmup, a.iters)
             entry.update({"vif": vf, "metrics": met, "ciede_over_vif": round(t["avg_ms"] / vf["avg_ms"], 3),
                           "ciede_over_metrics": round(t["avg_ms"] / met["avg_ms"], 2)})
             res["vif_ms"], res["metrics_ms"] = vf["avg_ms"], met["avg_ms"]
@@ -148,29 +125,16 @@ def one_format(fmt, a, dev):
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--frames", type=int, default=600)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--iters", type=int, default=10)
-    ap.add_argument("--out", default=None)
+    ap = callbench.parser(600, 2, 10)
     a = ap.parse_args(argv)
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("ciede_bench: no GPU visible (a timing needs the MI355X)")
-    dev = torch.device("cuda", 0)
-    torch.manual_seed(910)
-    res = {"tool": "ciede_bench", "device": torch.cuda.get_device_name(0), "w": W, "h": H, "frames": a.frames,
-           "warmup": a.warmup,
-           "timer": "HIP events around one call over the clip: every launch of pp_ciede (ciede_kernel, ciede_finalize) "
-                    "/ of pp_vif (luma) / of pp_metrics (three planes)",
-           "fp64_issue_rate_per_s": FP64_ISSUE_RATE, "fp64_instr_per_position_static": FP64_INSTR_POSITION,
-           "formats": [one_format(f, a, dev) for f in ("yuv420p", "yuv422p10le")]}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    dev = callbench.require_gpu("ciede_bench", seed=910)
+    res = callbench.header(
+        "ciede_bench", a,
+        timer="HIP events around one call over the clip: every launch of pp_ciede (ciede_kernel, ciede_finalize) "
+              "/ of pp_vif (luma) / of pp_metrics (three planes)",
+        fp64_issue_rate_per_s=callbench.FP64_ISSUE_RATE, fp64_instr_per_position_static=FP64_INSTR_POSITION,
+        formats=[one_format(f, a, dev) for f in ("yuv420p", "yuv422p10le")])
+    callbench.emit(res, a.out)
     return 0
 
 

@@ -23,36 +23,13 @@ Prints one JSON line; a measurement, not a gate; it fails without a GPU.
 
   python tools/dctenergy_bench.py [--frames 600] [--out profiles/dctenergy/NAME.json]
 """
-import argparse
-import json
-import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (os.path.join(ROOT, "processing-chain_amd"), os.path.join(ROOT, "tests")):
-    sys.path.insert(0, p)
+import callbench
 
-HBM_SPEC, HBM_COPY = 8.0e12, 6.29e12
 CHECKED = 3  # frames compared with the CPU
 MADS_PER_BLOCK = 2 * 32 * 32 * 16
-W, H = 1920, 1080
-
-
-def timed(fn, warmup, iters):
-    import torch
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(iters):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return {"avg_ms": round(sum(ms) / len(ms), 3), "min_ms": round(min(ms), 3), "max_ms": round(max(ms), 3),
-            "launches": len(ms)}
+W, H = callbench.W, callbench.H
 
 
 def fill(luma, content, depth, dev):
@@ -100,11 +77,11 @@ def one_case(depth, content, luma, a, dev, peak_mads):
     if got != want:
         raise SystemExit("dctenergy_bench: %d-bit %s differs from the restatement: %r against %r" % (depth, content, got, want))
     E, T, L = dctenergy.pool(keep["dct"].cpu().numpy(), W, H)
-    de = timed(dct_pass, a.warmup, a.iters)
+    de = callbench.timed(dct_pass, a.warmup, a.iters)
     res = {"bitdepth": depth, "content": content, "dct_energy": de,
            "clip": {"dct_energy_y": float(E.mean()), "dct_temporal_y": float(T.mean()), "brightness_y": float(L.mean())}}
     if content == "noise":  # the neighbours' times do not depend on the content either: once per depth
-        mo, si, ms = (timed(f, a.warmup, a.iters) for f in (motion_pass, siti_pass, msssim_pass))
+        mo, si, ms = (callbench.timed(f, a.warmup, a.iters) for f in (motion_pass, siti_pass, msssim_pass))
         res.update({"motion": mo, "siti": si, "ms_ssim": ms,
                     "dct_energy_over_motion": round(de["avg_ms"] / mo["avg_ms"], 3),
                     "dct_energy_over_siti": round(de["avg_ms"] / si["avg_ms"], 3),
@@ -114,24 +91,17 @@ def one_case(depth, content, luma, a, dev, peak_mads):
     bx, by = dctenergy.geometry(W, H)
     mads = n * bx * by * MADS_PER_BLOCK  # lane operations
     res.update({"algorithmic_bytes": traffic, "tb_per_s": round(rate / 1e12, 3),
-                "share_of_hbm_spec": round(rate / HBM_SPEC, 3), "share_of_hbm_copy": round(rate / HBM_COPY, 3),
+                "share_of_hbm_spec": round(rate / callbench.HBM_PEAK, 3), "share_of_hbm_copy": round(rate / callbench.HBM_COPY, 3),
                 "multiply_adds": mads, "share_of_int_mad_issue_rate": round(mads / (de["avg_ms"] * 1e-3) / peak_mads, 3),
                 "cpu_check_frames": CHECKED, "cpu_check": "equal"})
     return res
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--frames", type=int, default=600)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--iters", type=int, default=10)
-    ap.add_argument("--out", default=None)
+    ap = callbench.parser(600, 3, 10)
     a = ap.parse_args(argv)
+    dev = callbench.require_gpu("dctenergy_bench", seed=910)
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("dctenergy_bench: no GPU visible (a timing needs the MI355X)")
-    dev = torch.device("cuda", 0)
-    torch.manual_seed(910)
     prop = torch.cuda.get_device_properties(0)
     clock_hz = float(getattr(prop, "clock_rate", 2400000)) * 1e3
     peak = prop.multi_processor_count * 4 * 16 * clock_hz
@@ -141,18 +111,12 @@ def main(argv=None):
         for content in ("noise", "smooth", "constant"):
             cases.append(one_case(depth, content, luma, a, dev, peak))
         del luma
-    res = {"tool": "dctenergy_bench", "device": torch.cuda.get_device_name(0), "w": W, "h": H, "frames": a.frames,
-           "warmup": a.warmup, "compute_units": prop.multi_processor_count, "clock_hz": clock_hz,
-           "int_mad_lane_ops_per_s": peak,
-           "timer": "HIP events around one call over the clip: every launch of pp_dct_energy (dct_kernel, "
-                    "dct_finalize) / of pp_motion / of pp_siti / of pp_ms_ssim (the luma against itself)",
-           "hbm_spec_bytes_per_s": HBM_SPEC, "hbm_copy_bytes_per_s": HBM_COPY, "cases": cases}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    res = callbench.header(
+        "dctenergy_bench", a, compute_units=prop.multi_processor_count, clock_hz=clock_hz, int_mad_lane_ops_per_s=peak,
+        timer="HIP events around one call over the clip: every launch of pp_dct_energy (dct_kernel, "
+              "dct_finalize) / of pp_motion / of pp_siti / of pp_ms_ssim (the luma against itself)",
+        hbm_spec_bytes_per_s=callbench.HBM_PEAK, hbm_copy_bytes_per_s=callbench.HBM_COPY, cases=cases)
+    callbench.emit(res, a.out)
     return 0
 
 

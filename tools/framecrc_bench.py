@@ -18,63 +18,23 @@ measurement, not a gate; it fails without a GPU.
 
   python tools/framecrc_bench.py [--frames 600] [--out profiles/framecrc/NAME.json]
 """
-import argparse
-import json
-import os
-import statistics
 import sys
 import time
 import zlib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "processing-chain_amd"))
-
-HBM_PEAK = 8.0e12  # B/s
-
-
-def timed_round_robin(fns, warmup, iters):
-    """Event-pair times (ms) of each callable, the callables taken in turn."""
-    import torch
-    for _ in range(warmup):
-        for fn in fns.values():
-            fn()
-    torch.cuda.synchronize()
-    ms = {k: [] for k in fns}
-    for _ in range(iters):
-        for k, fn in fns.items():
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            b.synchronize()
-            ms[k].append(a.elapsed_time(b))
-    return ms
-
-
-def stats(ms, nbytes):
-    avg = sum(ms) / len(ms)
-    return {"avg_launch_ms": round(avg, 4), "median_ms": round(statistics.median(ms), 4), "min_ms": round(min(ms), 4),
-            "max_ms": round(max(ms), 4), "bytes": nbytes, "GBps": round(nbytes / avg / 1e6, 1),
-            "frac": round(nbytes / (avg * 1e-3) / HBM_PEAK, 4)}
+import callbench
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--frames", type=int, default=600)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--out", default=None)
+    ap = callbench.parser(600, 3, 20)
     a = ap.parse_args(argv)
     if a.iters < 20:
         ap.error("--iters must be at least 20")
+    dev = callbench.require_gpu("framecrc_bench", seed=910)
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("framecrc_bench: no GPU visible (a timing needs the MI355X)")
     from pixpath import formats, ops
     from pixpath.frames import FrameBatch
-    fmt, w, h, n = "yuv422p10le", 1920, 1080, a.frames
-    dev = torch.device("cuda", 0)
-    torch.manual_seed(910)
+    fmt, w, h, n = "yuv422p10le", callbench.W, callbench.H, a.frames
     ref, dist = FrameBatch(fmt, w, h, n, device=dev), FrameBatch(fmt, w, h, n, device=dev)
     for p in range(3):
         r16, d16 = ref.planes[p].view(torch.int16), dist.planes[p].view(torch.int16)
@@ -112,30 +72,24 @@ def main(argv=None):
         "pp_metrics_yuv420p": lambda: out.__setitem__("n", ops.metrics(b420, d420)),
         "adler_v210": lambda: out.__setitem__("c", ops.frame_adler32(bv210)),
     }
-    ms = timed_round_robin(fns, a.warmup, a.iters)
+    ms = callbench.timed_round_robin(fns, a.warmup, a.iters)
     nbytes = {"adler_yuv422p10le": n * formats.frame_bytes(fmt, w, h), "pp_siti_luma": n * w * h * 2,
               "pp_metrics": 2 * n * formats.frame_bytes(fmt, w, h),
               "adler_yuv420p": n * formats.frame_bytes("yuv420p", w, h),
               "pp_metrics_yuv420p": 2 * n * formats.frame_bytes("yuv420p", w, h),
               "adler_v210": n * formats.frame_bytes("v210", w, h)}
-    res = {"tool": "framecrc_bench", "device": torch.cuda.get_device_name(0), "w": w, "h": h, "frames": n,
-           "warmup": a.warmup, "iters": a.iters,
-           "timer": "HIP events around one ops call (kernel + finalize), the six calls taken in turn",
-           "frame0_equals_zlib": check}
+    res = callbench.header("framecrc_bench", a, callbench.HEAD + ("iters",),
+                           timer="HIP events around one ops call (kernel + finalize), the six calls taken in turn",
+                           frame0_equals_zlib=check)
     for k in fns:
-        res[k] = stats(ms[k], nbytes[k])
+        res[k] = callbench.throughput(ms[k], nbytes[k], median=True)
     res["adler_vs_metrics_per_byte"] = {k: round(res[k]["GBps"] / res["pp_metrics"]["GBps"], 3)
                                         for k in fns if k.startswith("adler")}
     res["adler_yuv420p_vs_metrics_yuv420p_per_byte"] = round(res["adler_yuv420p"]["GBps"] /
                                                              res["pp_metrics_yuv420p"]["GBps"], 3)
     res["zlib_adler32_one_thread"] = {"bytes": len(frame), "ms_per_frame": round(cpu_s * 1e3, 4),
                                       "GBps": round(len(frame) / cpu_s / 1e9, 3)}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    callbench.emit(res, a.out)
     return 0
 
 

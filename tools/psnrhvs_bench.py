@@ -26,36 +26,13 @@ Prints one JSON line; a measurement, not a gate; it fails without a GPU.
 
   python tools/psnrhvs_bench.py [--frames 600] [--out profiles/psnrhvs/NAME.json]
 """
-import argparse
-import json
-import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "processing-chain_amd"))
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import callbench
 
 FP64_INSTR_LANE = 470  # v_*_f64 in hvs_kernel<uint8_t, true>'s disassembly (profiles/psnrhvs/kernel_resources.md)
 FP64_INSTR_BLOCK = 8 * FP64_INSTR_LANE
-FP64_ISSUE_RATE = 256 * 4 * 16 * 2.4e9
-W, H = 1920, 1080
-
-
-def timed(fn, warmup, iters):
-    import torch
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(iters):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return {"avg_ms": round(sum(ms) / len(ms), 3), "min_ms": round(min(ms), 3), "max_ms": round(max(ms), 3),
-            "launches": len(ms)}
+W, H = callbench.W, callbench.H
 
 
 def fill(kind, fmt, n, dev):
@@ -121,7 +98,7 @@ def one_format(fmt, a, dev):
             torch.cuda.synchronize()
             got = keep["hvs"].cpu().numpy()
             rel, relm = check(fmt, step, ref, dist, got)
-            t = timed(hvs_pass, a.warmup, a.iters)
+            t = callbench.timed(hvs_pass, a.warmup, a.iters)
             nblk = n * sum(psnrhvs.blocks(fmt, W, H, step))
             rate = nblk * FP64_INSTR_BLOCK / (t["avg_ms"] * 1e-3)
             pooled = psnrhvs.summarize(got, W, H, None, fmt, step)["mean"]
@@ -131,12 +108,13 @@ def one_format(fmt, a, dev):
                 "psnr_hvs": t, "blocks": nblk, "ns_per_block": round(t["avg_ms"] * 1e6 / nblk, 4),
                 "restatement_max_rel_hvs": rel, "restatement_max_hvsm_over_hvs": relm,
                 "psnr_hvs_all": json_value(pooled["psnr_hvs_all"]), "psnr_hvsm_all": json_value(pooled["psnr_hvsm_all"]),
-                "fp64_instr_per_s": float("%.4g" % rate), "share_of_fp64_issue_rate": round(rate / FP64_ISSUE_RATE, 3),
+                "fp64_instr_per_s": float("%.4g" % rate), 
+                "share_of_fp64_issue_rate": round(rate / callbench.FP64_ISSUE_RATE, 3),
                 "algorithmic_bytes": traffic, "tb_per_s": round(traffic / (t["avg_ms"] * 1e-3) / 1e12, 3)}
         if kind == "noise":
             for name, fn in (("adm", lambda: ops.adm(ref, dist)), ("ciede", lambda: ops.ciede(ref, dist, fmt)),
                              ("metrics", lambda: ops.metrics(ref, dist))):
-                entry[name] = timed(lambda fn=fn: keep.__setitem__("o", fn()), a.warmup, a.iters)
+                entry[name] = callbench.timed(lambda fn=fn: keep.__setitem__("o", fn()), a.warmup, a.iters)
                 res[name + "_ms"] = entry[name]["avg_ms"]
         for step in psnrhvs.STEPS:
             e = entry["step%d" % step]
@@ -149,29 +127,16 @@ def one_format(fmt, a, dev):
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--frames", type=int, default=600)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--iters", type=int, default=10)
-    ap.add_argument("--out", default=None)
+    ap = callbench.parser(600, 2, 10)
     a = ap.parse_args(argv)
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("psnrhvs_bench: no GPU visible (a timing needs the MI355X)")
-    dev = torch.device("cuda", 0)
-    torch.manual_seed(910)
-    res = {"tool": "psnrhvs_bench", "device": torch.cuda.get_device_name(0), "w": W, "h": H, "frames": a.frames,
-           "warmup": a.warmup,
-           "timer": "HIP events around one call over the clip: every launch of pp_psnr_hvs (hvs_kernel, hvs_finalize) "
-                    "/ of pp_adm (luma) / of pp_ciede and pp_metrics (three planes)",
-           "fp64_issue_rate_per_s": FP64_ISSUE_RATE, "fp64_instr_per_block_static": FP64_INSTR_BLOCK,
-           "formats": [one_format(f, a, dev) for f in ("yuv420p", "yuv422p10le")]}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    dev = callbench.require_gpu("psnrhvs_bench", seed=910)
+    res = callbench.header(
+        "psnrhvs_bench", a,
+        timer="HIP events around one call over the clip: every launch of pp_psnr_hvs (hvs_kernel, hvs_finalize) "
+              "/ of pp_adm (luma) / of pp_ciede and pp_metrics (three planes)",
+        fp64_issue_rate_per_s=callbench.FP64_ISSUE_RATE, fp64_instr_per_block_static=FP64_INSTR_BLOCK,
+        formats=[one_format(f, a, dev) for f in ("yuv420p", "yuv422p10le")])
+    callbench.emit(res, a.out)
     return 0
 
 

@@ -21,43 +21,12 @@ measurement, not a gate; it fails without a GPU.
 
   python tools/stats_bench.py [--frames 600] [--out profiles/stats/NAME.json]
 """
-import argparse
-import json
 import os
-import statistics
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "processing-chain_amd"))
+import callbench
 
-HBM_PEAK = 8.0e12  # B/s
 CONTENTS = ("noise", "smooth", "constant")
-
-
-def timed_round_robin(fns, warmup, iters):
-    """Event-pair times (ms) of each callable, the callables taken in turn."""
-    import torch
-    for _ in range(warmup):
-        for fn in fns.values():
-            fn()
-    torch.cuda.synchronize()
-    ms = {k: [] for k in fns}
-    for _ in range(iters):
-        for k, fn in fns.items():
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            b.synchronize()
-            ms[k].append(a.elapsed_time(b))
-    return ms
-
-
-def summary(ms, nbytes):
-    avg = sum(ms) / len(ms)
-    return {"avg_launch_ms": round(avg, 4), "median_ms": round(statistics.median(ms), 4), "min_ms": round(min(ms), 4),
-            "max_ms": round(max(ms), 4), "bytes": nbytes, "TBps": round(nbytes / avg / 1e9, 3),
-            "frac": round(nbytes / (avg * 1e-3) / HBM_PEAK, 4)}
 
 
 def fill(batch, content, seed):
@@ -107,30 +76,23 @@ def verify(batch):
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--frames", type=int, default=600)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--iters", type=int, default=20)
+    ap = callbench.parser(600, 3, 20)
     ap.add_argument("--contents", default=",".join(CONTENTS))
-    ap.add_argument("--out", default=None)
     a = ap.parse_args(argv)
     if a.iters < 20:
         ap.error("--iters must be at least 20")
+    dev = callbench.require_gpu("stats_bench")
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("stats_bench: no GPU visible (a timing needs the MI355X)")
     from pixpath import _native, formats, ops
     from pixpath.frames import FrameBatch
-    w, h, n = 1920, 1080, a.frames
-    dev = torch.device("cuda", 0)
+    w, h, n = callbench.W, callbench.H, a.frames
     b10, b8 = FrameBatch("yuv422p10le", w, h, n, device=dev), FrameBatch("yuv420p", w, h, n, device=dev)
     nb10, nb8 = n * formats.frame_bytes("yuv422p10le", w, h), n * formats.frame_bytes("yuv420p", w, h)
-    res = {"tool": "stats_bench", "device": torch.cuda.get_device_name(0), "w": w, "h": h, "frames": n,
-           "warmup": a.warmup, "iters": a.iters,
-           "timer": "HIP events around one ops call (kernel + finalize), the calls taken in turn",
-           "bytes": "algorithmic: every sample once; the histograms (%d B for yuv422p10le) are not counted"
-                    % (n * 3 * 1024 * 4),
-           "library": os.path.basename(_native.LIB_PATH)}
+    res = callbench.header("stats_bench", a, callbench.HEAD + ("iters",),
+                           timer="HIP events around one ops call (kernel + finalize), the calls taken in turn",
+                           bytes="algorithmic: every sample once; the histograms (%d B for yuv422p10le) are not counted"
+                                 % (n * 3 * 1024 * 4),
+                           library=os.path.basename(_native.LIB_PATH))
     if "PIXPATH_LIB" in os.environ:  # a measurement build: record its knobs
         res["PIXPATH_STATS_ABL"] = os.environ.get("PIXPATH_STATS_ABL", "0")
     out = {}
@@ -150,20 +112,16 @@ def main(argv=None):
             "stats_nosad_yuv420p": lambda: out.__setitem__("f", ops.frame_stats(b8, want_sad=False)),
             "adler_yuv420p": lambda: out.__setitem__("g", ops.frame_adler32(b8)),
         }
-        ms = timed_round_robin(fns, a.warmup, a.iters)
-        r = {k: summary(ms[k], n * w * h * 2 if k == "pp_siti_luma" else nb10 if "10le" in k else nb8) for k in fns}
+        ms = callbench.timed_round_robin(fns, a.warmup, a.iters)
+        r = {k: callbench.throughput(ms[k], n * w * h * 2 if k == "pp_siti_luma" else nb10 if "10le" in k else nb8,
+                                     median=True, rate=("TBps", 1e9, 3)) for k in fns}
         r["vs_adler"] = {k: round(r["adler_" + k.split("_")[-1]]["avg_launch_ms"] / r[k]["avg_launch_ms"], 3)
                          for k in fns if k.startswith("stats")}
         res[content] = r
     if "constant" in res and "noise" in res:
         res["constant_vs_noise_time"] = {k: round(res["constant"][k]["avg_launch_ms"] / res["noise"][k]["avg_launch_ms"], 3)
                                          for k in res["noise"] if k.startswith("stats")}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    callbench.emit(res, a.out)
     return 0
 
 

@@ -15,59 +15,23 @@ measurement, not a gate; it fails without a GPU.
 
   python tools/unpack_bench.py [--frames 600] [--out profiles/unpack/NAME.json]
 """
-import argparse
-import json
-import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "processing-chain_amd"))
-
-HBM_PEAK = 8.0e12  # B/s
-
-
-def timed(fn, warmup, iters):
-    import torch
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(iters):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return ms
-
-
-def stats(ms, nbytes):
-    avg = sum(ms) / len(ms)
-    return {"avg_launch_ms": round(avg, 4), "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4),
-            "bytes": nbytes, "GBps": round(nbytes / avg / 1e6, 1), "frac": round(nbytes / (avg * 1e-3) / HBM_PEAK, 4)}
+import callbench
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--frames", type=int, default=600)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--out", default=None)
+    ap = callbench.parser(600, 3, 20)
     a = ap.parse_args(argv)
     if a.iters < 20:
         ap.error("--iters must be at least 20")
+    dev = callbench.require_gpu("unpack_bench", seed=210)
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("unpack_bench: no GPU visible (a timing needs the MI355X)")
     from pixpath import formats, ops
     from pixpath.frames import FrameBatch
-    w, h, n = 1920, 1080, a.frames
-    dev = torch.device("cuda", 0)
-    torch.manual_seed(210)
-    res = {"tool": "unpack_bench", "device": torch.cuda.get_device_name(0), "w": w, "h": h, "frames": n,
-           "warmup": a.warmup, "iters": a.iters,
-           "timer": "HIP events around one pp_unpack_execute / one pp_cpvs_execute call (one kernel each)"}
+    w, h, n = callbench.W, callbench.H, a.frames
+    res = callbench.header("unpack_bench", a, callbench.HEAD + ("iters",),
+                           timer="HIP events around one pp_unpack_execute / one pp_cpvs_execute call (one kernel each)")
     for planar, packed in (("yuv422p10le", "v210"), ("yuv422p", "uyvy422")):
         src = FrameBatch(planar, w, h, n, device=dev)
         lo, hi = (64, 941) if planar == "yuv422p10le" else (16, 236)
@@ -78,13 +42,13 @@ def main(argv=None):
         pk = FrameBatch(packed, w, h, n, device=dev)
         back = FrameBatch(planar, w, h, n, device=dev)
         pbytes, ubytes = formats.frame_bytes(planar, w, h), formats.frame_bytes(packed, w, h)
-        pack_ms = timed(lambda: ops.cpvs(src, w, h, dst=pk), a.warmup, a.iters)
-        unpack_ms = timed(lambda: ops.unpack(pk, dst=back), a.warmup, a.iters)
+        pack_ms = callbench.times(lambda: ops.cpvs(src, w, h, dst=pk), a.warmup, a.iters)
+        unpack_ms = callbench.times(lambda: ops.unpack(pk, dst=back), a.warmup, a.iters)
         torch.cuda.synchronize()
         same = all(bool(torch.equal(back.view(p), src.view(p))) for p in range(3))
         entry = {"algorithmic_bytes_per_frame": pbytes + ubytes,
-                 "unpack": stats(unpack_ms, n * (pbytes + ubytes)),
-                 "pack_cpvs": stats(pack_ms, n * (pbytes + ubytes)),
+                 "unpack": callbench.throughput(unpack_ms, n * (pbytes + ubytes)),
+                 "pack_cpvs": callbench.throughput(pack_ms, n * (pbytes + ubytes)),
                  "round_trip_equal": same}
         entry["unpack_time_per_byte_vs_pack"] = round(entry["unpack"]["avg_launch_ms"] /
                                                       entry["pack_cpvs"]["avg_launch_ms"], 3)
@@ -92,17 +56,12 @@ def main(argv=None):
         if packed == "v210":
             luma = torch.empty((n, h, w), dtype=torch.uint16, device=dev)
             lbytes = ubytes + w * h * 2
-            luma_ms = timed(lambda: ops.unpack(pk, luma_only=True, dst=luma), a.warmup, a.iters)
+            luma_ms = callbench.times(lambda: ops.unpack(pk, luma_only=True, dst=luma), a.warmup, a.iters)
             torch.cuda.synchronize()
-            res["v210_to_luma"] = {"algorithmic_bytes_per_frame": lbytes, "unpack": stats(luma_ms, n * lbytes),
+            res["v210_to_luma"] = {"algorithmic_bytes_per_frame": lbytes, "unpack": callbench.throughput(luma_ms, n * lbytes),
                                    "luma_equal": bool(torch.equal(luma, src.view(0)))}
         del src, pk, back
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    callbench.emit(res, a.out)
     return 0
 
 
